@@ -12,9 +12,13 @@ Multi-GPU: one process per GPU (torchrun), each rank owns its own 1M-codeword sh
 embarrassingly parallel, so there is no data-path collective (weak scaling); a barrier brackets the
 timed region and the max time over ranks is taken.
 
-Extra objects on the JSON line: "roofline" (dominant API call, algorithmic bytes / HIP-event
-time vs 8 TB/s HBM), "cpu_baseline" (rank 0, N=1: the reference codec compiled from
-/root/reference -- or the oracle restatement -- on the host cores, bounded sample).
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and
+prints the JSON line with the headline figure.  `--dump-outputs DIR` also writes what the last timed
+step left in the caller's arrays as DIR/<name>.npy (dump_outputs below).  `--full` adds the figures
+that take runs of their own: "roofline" (dominant API call, algorithmic bytes / HIP-event time vs
+8 TB/s HBM, from a second event-bracketed pass), the north_star extras of the N=1 C2 line
+(c2_extras) and "cpu_baseline" (rank 0, N=1: the reference codec of oracle/_ref -- or the oracle
+restatement -- on the host cores, bounded sample).
 """
 from __future__ import annotations
 
@@ -42,6 +46,38 @@ def log(*a):
 
 
 SHARE_GPUS = False              # --share-gpus: ranks may share a GPU (harness test only)
+DUMP_ARRAY_BYTES = 24 << 20     # --dump-outputs: float32 bytes kept per array (two big arrays + result < 64 MB)
+DUMP_SEED = 0xD0F5              # --dump-outputs: seed of the row sample of an array over that size
+
+
+def dump_outputs(dirname, arrays, rank=0, world=1):
+    """--dump-outputs: write the arrays a caller of the timed path holds after the last timed step
+    as DIR/<name>.npy, float32 (8- and 16-bit symbols and the int32 results are exact in it).  An
+    array over DUMP_ARRAY_BYTES is cut to a fixed, seeded sample of its rows (the same rows in every
+    run of the same shape); the row numbers go to DIR/<name>_rows.npy (float64).  With more than one
+    rank each rank writes its own shard as <name>_rank<r>."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    total = 0
+    for name, t in arrays.items():
+        nrows = t.shape[0]
+        per_row = 4 * max(1, t[0].numel()) if nrows else 4
+        keep = max(1, DUMP_ARRAY_BYTES // per_row)
+        if nrows > keep:
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(nrows, keep, replace=False))
+            t = t[torch.from_numpy(rows).to(t.device)]
+            np.save(os.path.join(dirname, f"{name}_rows{sfx}.npy"), rows.astype(np.float64))
+            total += rows.size * 8
+        a = t.cpu().numpy()
+        if a.dtype == np.int16:                       # 16-bit symbols are stored as int16 tensors
+            a = a.view(np.uint16)
+        a = a.astype(np.float32)
+        np.save(os.path.join(dirname, f"{name}{sfx}.npy"), a)
+        total += a.nbytes
+    assert total <= 64 << 20, total
+    log(f"bench: wrote {sorted(arrays)} to {dirname} ({total / 1e6:.1f} MB)")
 
 
 def bench_device(local):
@@ -329,6 +365,9 @@ def bench_rs_errors(args):
     for s_ in range(args.steps):
         step(evs[s_])
     torch.cuda.synchronize()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"encoded": clean.view(tdt), "decoded": work,
+                                         "result": result}, rank, world)
     enc_ms = sum(e[0].elapsed_time(e[1]) for e in evs) / args.steps
     dec_ms = sum(e[1].elapsed_time(e[2]) for e in evs) / args.steps
     t = shard.max_over_ranks(enc_ms + dec_ms)
@@ -417,6 +456,9 @@ def bench_c5(args):
     for s in range(args.steps):
         step(evs[s])
     torch.cuda.synchronize()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"encoded": clean, "decoded": work, "result": result},
+                     rank, world)
     enc_ms = sum(e[0].elapsed_time(e[1]) for e in evs) / args.steps
     dec_ms = sum(e[1].elapsed_time(e[2]) for e in evs) / args.steps
     t = shard.max_over_ranks(enc_ms + dec_ms)
@@ -666,7 +708,7 @@ def c5_extra(gen, steps=5, ncw=8 << 20):
 
 
 def c2_extras(codec, args):
-    """The north_star / SURVEY 8(d) figures the driver's default run carries beside the headline
+    """The north_star / SURVEY 8(d) figures a --full run of the N=1 C2 line carries beside the headline
     (all timed in the same process, HIP events): shard batches at S = 1 KiB and 1 MiB, C2 at 4M
     codewords (1.07 GB, past the 256 MiB Infinity Cache), the C3 decode (8 errors + 4 erasures per
     codeword), C4 (RS(65535,65503), 64k codewords), C5 (BCH(1023,983,4), 8M codewords), and the
@@ -776,6 +818,8 @@ def bench_shards(args):
     shard bytes and each call's HBM fraction."""
     import torch
     import ezrs
+    if args.dump_outputs:
+        raise SystemExit("bench: --dump-outputs is not available for the shard sweep")
     local = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     torch.cuda.set_device(local)
@@ -807,12 +851,21 @@ def main():
     ap.add_argument("--spinup", type=float, default=0.5,
                     help="seconds of untimed device spin-up (whole steps) before the counted warm-up")
     ap.add_argument("--ncw", type=int, default=1 << 20, help="codewords per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the roofline pass (per-call HIP-event averages), the "
+                         "extra figures of the N=1 C2 line (--no-extras drops them) and the CPU "
+                         "baselines (--no-cpu-baseline drops them); a plain run does none of these")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step left in the caller's "
+                         "arrays (codewords with their parity, decode results) as DIR/<name>.npy, "
+                         "float32, at most 64 MB (a fixed seeded row sample of a larger array)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baselines")
     ap.add_argument("--cpu-seconds", type=float, default=3.0,
                     help="seconds per CPU-baseline measurement (5 configs x 1/all threads)")
     ap.add_argument("--e2e", action="store_true", help="also time the host-memory pipeline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the extra figures of the default N=1 C2 run (shards 1 KiB / 1 MiB, "
+                    help="with --full: skip the extra figures of the N=1 C2 run (shards 1 KiB / 1 MiB, "
                          "C2 at 4M codewords, C3 decode, host-memory rates)")
     ap.add_argument("--workload", choices=("c2", "c1", "c3", "c4", "c5", "shards"), default="c2",
                     help="c2: the headline RS(255,223) line; c1: the same for RS(255,251); c3: "
@@ -903,39 +956,46 @@ def main():
     bad = int((result != 0).sum())
     if bad:
         raise SystemExit(f"rank {rank}: {bad} encoded codewords did not decode clean")
-    # per-call averages for the roofline: 25 untimed steps are enqueued first (the check above
-    # idled the GPU; they cover the ~2 ms clock ramp, so the first event is recorded on a busy GPU),
-    # then KC = max(K, 200) encodes and KC (clean) decodes of the same batch back to back, bracketed
-    # by three HIP events on the launch stream, one synchronize at the end (r05k: with K = 20 and 3
-    # untimed steps the decode average read 0.086 ms against the kernel trace's 0.072)
-    for _ in range(25):
-        step()
-    kc = max(args.steps, 200)
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-    ev[0].record(stream)
-    for _ in range(kc):
-        codec.encode(cw, k, stream=stream)
-    ev[1].record(stream)
-    for _ in range(kc):
-        codec.decode(cw, k, result=result, stream=stream)
-    ev[2].record(stream)
-    ev[2].synchronize()
-    enc_ms = ev[0].elapsed_time(ev[1]) / kc
-    dec_ms = ev[1].elapsed_time(ev[2]) / kc
-
+    if args.dump_outputs:
+        # what the last timed step left with the caller: the batch with its parity written in
+        # place (decode found it clean and changed nothing) and the per-codeword decode results
+        dump_outputs(args.dump_outputs, {"codewords": cw, "result": result}, rank, world)
     total_cw = ncw * world * args.steps
     value = total_cw * n / elapsed / 1e9
-    if enc_ms >= dec_ms:
-        dom, ms, per_cw = "ezrs_encode", enc_ms, enc_bytes
-    else:
-        dom, ms, per_cw = "ezrs_decode", dec_ms, dec_bytes
-    achieved = ncw * per_cw / (ms * 1e-3) / 1e9
-    roofline = {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
-                "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                "traffic": load_traffic(args.workload, dom, ncw), "kernel": dom,
-                "algorithmic_bytes_per_launch": ncw * per_cw,
-                "avg_ms": {"ezrs_encode": round(enc_ms, 4), "ezrs_decode": round(dec_ms, 4)},
-                "avg_calls": kc}
+
+    roofline = None
+    if args.full:
+        # per-call averages for the roofline: 25 untimed steps are enqueued first (the check above
+        # idled the GPU; they cover the ~2 ms clock ramp, so the first event is recorded on a busy
+        # GPU), then KC = max(K, 200) encodes and KC (clean) decodes of the same batch back to back,
+        # bracketed by three HIP events on the launch stream, one synchronize at the end (r05k: with
+        # K = 20 and 3 untimed steps the decode average read 0.086 ms against the kernel trace's
+        # 0.072)
+        for _ in range(25):
+            step()
+        kc = max(args.steps, 200)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        ev[0].record(stream)
+        for _ in range(kc):
+            codec.encode(cw, k, stream=stream)
+        ev[1].record(stream)
+        for _ in range(kc):
+            codec.decode(cw, k, result=result, stream=stream)
+        ev[2].record(stream)
+        ev[2].synchronize()
+        enc_ms = ev[0].elapsed_time(ev[1]) / kc
+        dec_ms = ev[1].elapsed_time(ev[2]) / kc
+        if enc_ms >= dec_ms:
+            dom, ms, per_cw = "ezrs_encode", enc_ms, enc_bytes
+        else:
+            dom, ms, per_cw = "ezrs_decode", dec_ms, dec_bytes
+        achieved = ncw * per_cw / (ms * 1e-3) / 1e9
+        roofline = {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+                    "traffic": load_traffic(args.workload, dom, ncw), "kernel": dom,
+                    "algorithmic_bytes_per_launch": ncw * per_cw,
+                    "avg_ms": {"ezrs_encode": round(enc_ms, 4), "ezrs_decode": round(dec_ms, 4)},
+                    "avg_calls": kc}
 
     e2e = None
     if args.e2e and rank == 0:
@@ -959,11 +1019,11 @@ def main():
             log(f"host-memory ({name}) encode+decode: {e2e[name]} GB/s")
 
     extras = None
-    if world == 1 and args.workload == "c2" and not args.k and not args.no_extras:
+    if args.full and world == 1 and args.workload == "c2" and not args.k and not args.no_extras:
         extras = c2_extras(codec, args)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baselines(args.cpu_seconds)
 
     if rank == 0:

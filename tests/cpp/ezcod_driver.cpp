@@ -1,7 +1,7 @@
 // ezcod_driver.cpp -- exercises the reference's ezcod C API (ezcod.h: ezcod_3_{10,11,12}_{encode,
 // decode}, implemented in the reference's ezcod.C over ezpwd::RS<31,31-P>).  Built twice:
 // against the reference's own headers (oracle/_ref/ezcod_ref: the fixture generator) and against
-// this repository's include/ (tests/cpp/_bin/ezcod_gpu: ezcod.C unchanged, its RS on the GPU).
+// this repository's include/ (oracle/_ref/bin/ezcod_gpu: ezcod.C unchanged, its RS on the GPU).
 // Prints one line per call; the two builds must print the same lines.
 #include <cstdint>
 #include <cstdio>

@@ -67,7 +67,7 @@ def test_reference_bch_programs_pass_on_gpu(tmp_path, name):
     import torch
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    prebuilt = os.path.join(ROOT, "tests", "cpp", "_bin", name)
+    prebuilt = os.path.join(ROOT, "oracle", "_ref", "bin", name)
     exe = prebuilt if os.path.exists(prebuilt) else _build(tmp_path, name)
     p = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert p.returncode == 0 and "All tests passed." in p.stdout, p.stdout[-3000:]

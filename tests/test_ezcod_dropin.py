@@ -8,7 +8,7 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "tests", "cpp", "_bin", "ezcod_gpu")
+EXE = os.path.join(ROOT, "oracle", "_ref", "bin", "ezcod_gpu")
 GOLD = os.path.join(ROOT, "tests", "golden", "ezcod_ref.txt")
 
 

@@ -1,4 +1,4 @@
-"""The reference's own RS harnesses, compiled unchanged against the drop-in (tests/cpp/harness.mk,
+"""The reference's own RS harnesses, compiled unchanged against the drop-in (oracle/dropin.mk,
 built by __graft_entry__.build()), run on the GPU:
 
   rsexercise  rsexercise.C + exercise.H: 12 codecs (RS(255,K), RS_CCSDS, RS_CCSDS_CONV, RS<511>,
@@ -23,7 +23,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-BIN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "cpp", "_bin")
+BIN = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "bin")
 
 
 def _run(name, timeout):

@@ -11,7 +11,7 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "tests", "cpp", "_bin")
+BIN = os.path.join(ROOT, "oracle", "_ref", "bin")
 LIBDIR = os.path.join(ROOT, "ezpwd-reed-solomon_amd", "lib")
 REF = "/root/reference"
 

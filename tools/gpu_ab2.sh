@@ -16,7 +16,7 @@ for rep in 1 2; do
           -k "c2_past or RS_255_223 or (bulk and 223 and not CCSDS)" > $OUT/pytest_$v.log 2>&1
       rc=$?; echo "variant $v parity rc=$rc: $(tail -n 1 $OUT/pytest_$v.log)"; [ $rc -eq 0 ] || exit $rc
     fi
-    timeout -k 10 200 python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-extras > $OUT/bench_${v}_$rep.json 2> $OUT/bench_${v}_$rep.err
+    timeout -k 10 200 python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-extras > $OUT/bench_${v}_$rep.json 2> $OUT/bench_${v}_$rep.err
     rc=$?; [ $rc -eq 0 ] || { echo "bench $v rc=$rc"; tail -3 $OUT/bench_${v}_$rep.err; exit $rc; }
     python3 -c "
 import json; d=json.loads(open('$OUT/bench_${v}_$rep.json').read().splitlines()[-1])

@@ -16,6 +16,6 @@ run() {  # name timeout cmd...
 cd $GRAFT_REPO_ROOT
 run pytest 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread
 run smoke 240 python -c "import __graft_entry__ as g; g.smoke()"
-run bench_driver 500 python bench.py --gpus 1 --steps 20 --warmup 5
-run bench_k200 500 python bench.py --steps 200 --warmup 20 --no-cpu-baseline
+run bench_driver 500 python bench.py --full --gpus 1 --steps 20 --warmup 5
+run bench_k200 500 python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline
 exit 0

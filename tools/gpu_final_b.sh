@@ -2,6 +2,7 @@
 # Round-end check, part B: kernel-trace summaries and FETCH_SIZE / WRITE_SIZE passes (one counter
 # group per run) of C2, C3, C4, C5 (1 M) and C5 at 8 M.  Usage: tools/gpu_final_b.sh <tag>
 set -u
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 TAG=${1:-final}; OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
 run() {
@@ -13,7 +14,7 @@ run() {
   [ $rc -eq 0 ] || { tail -n 3 $OUT/$name.log; exit $rc; }
 }
 cd /tmp
-B="python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-extras"
+B="python3 $ROOT/bench.py --full --no-cpu-baseline --no-extras"
 run prof_c2 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_c2 -o run -- $B --steps 20 --warmup 3
 run prof_c3 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_c3 -o run -- $B --workload c3 --steps 5 --warmup 1
 run prof_c4 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_c4 -o run -- $B --workload c4 --steps 2 --warmup 1

@@ -15,10 +15,10 @@ run() {
 }
 cd $GRAFT_REPO_ROOT
 run bench_shards 400 python bench.py --workload shards --steps 20 --warmup 3 --no-cpu-baseline
-run bench_c1 300 python bench.py --workload c1 --steps 200 --warmup 20 --no-cpu-baseline
+run bench_c1 300 python bench.py --full --workload c1 --steps 200 --warmup 20 --no-cpu-baseline
 run bench_c3 400 python bench.py --workload c3 --steps 20 --warmup 3 --no-cpu-baseline
 run bench_c4 400 python bench.py --workload c4 --steps 5 --warmup 1 --no-cpu-baseline
 run bench_c5 300 python bench.py --workload c5 --steps 200 --warmup 20 --no-cpu-baseline
 run bench_c5_8m 300 python bench.py --workload c5 --ncw 8388608 --steps 50 --warmup 5 --no-cpu-baseline
-run bench_driver 500 python bench.py --gpus 1 --steps 20 --warmup 5
+run bench_driver 500 python bench.py --full --gpus 1 --steps 20 --warmup 5
 exit 0

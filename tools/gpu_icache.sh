@@ -3,6 +3,7 @@
 # rocprofv3 --pmc pass per group (counters the box does not have are dropped from the group), then
 # a per-kernel summary.  Usage: [KFILT=regex] tools/gpu_icache.sh <tag> [extra bench args]
 set -u
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 TAG=${1:-icache}; shift || true
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT
@@ -23,7 +24,7 @@ for grp in "${GROUPS_[@]}"; do
   echo "== pass $i:$sel"
   [ -z "$sel" ] && continue
   timeout -s KILL 120 rocprofv3 --pmc $sel --output-format csv -d $OUT/p$i -o run -- \
-      python3 $GRAFT_REPO_ROOT/bench.py --steps 3 --warmup 1 --spinup 0 --no-cpu-baseline --no-extras "$@" \
+      python3 $ROOT/bench.py --full --steps 3 --warmup 1 --spinup 0 --no-cpu-baseline --no-extras "$@" \
       > $OUT/p$i.log 2>&1
   rc=$?
   echo "== pass $i rc=$rc"

@@ -3,11 +3,12 @@
 # counters each), then the phase stamps of the tile kernel on random data (tools/micro/pq_stamps).
 # Usage: tools/gpu_pmc2.sh <tag> [extra bench args]
 set -u
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 TAG=${1:-pmc2}; shift || true
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-B="python3 $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extras $*"
+B="python3 $ROOT/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-extras $*"
 GROUPS_=(
   "SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_MISC"
   "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_LDS_CMD_FIFO_FULL SQ_LDS_DATA_FIFO_FULL SQ_LDS_UNALIGNED_STALL SQ_VMEM_TA_ADDR_FIFO_FULL SQ_VMEM_TA_CMD_FIFO_FULL SQ_ACTIVE_INST_VMEM"

@@ -2,6 +2,7 @@
 # SQ counter passes of the C2 bench for the default library and a variant (EZRS_LIB_VARIANT), one
 # rocprofv3 --pmc run per counter group.  Usage: tools/gpu_pmc_ab.sh <tag> [variant]
 set -u
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 TAG=$1; V=${2:-}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
@@ -15,7 +16,7 @@ for lib in default $V; do
   i=0
   for grp in "${SETS[@]}"; do
     i=$((i+1))
-    timeout -s KILL 150 rocprofv3 --pmc $grp --output-format csv -d $OUT/$lib/p$i -o run -- python3 $GRAFT_REPO_ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $OUT/$lib.p$i.log 2>&1
+    timeout -s KILL 150 rocprofv3 --pmc $grp --output-format csv -d $OUT/$lib/p$i -o run -- python3 $ROOT/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $OUT/$lib.p$i.log 2>&1
     rc=$?; echo "$lib pass $i rc=$rc"; [ $rc -eq 0 ] || { tail -5 $OUT/$lib.p$i.log; exit $rc; }
   done
   python3 $GRAFT_REPO_ROOT/tools/pmc_summary.py $OUT/$lib > $OUT/$lib.summary.txt 2>&1 || true

@@ -3,6 +3,7 @@
 # bench run, then a per-kernel summary of the kernels matching KFILT.
 # Usage: KFILT=regex tools/gpu_pmc_groups.sh <tag> "<group1>" "<group2>" ... -- [bench args]
 set -u
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 TAG=$1; shift
 GROUPS_=()
 while [ $# -gt 0 ] && [ "$1" != "--" ]; do GROUPS_+=("$1"); shift; done
@@ -21,7 +22,7 @@ for grp in "${GROUPS_[@]}"; do
   echo "== pass $i:$sel"
   [ -z "$sel" ] && continue
   timeout -s KILL 120 rocprofv3 --pmc $sel --output-format csv -d $OUT/p$i -o run -- \
-      python3 $GRAFT_REPO_ROOT/bench.py --steps 3 --warmup 1 --spinup 0 --no-cpu-baseline --no-extras "$@" \
+      python3 $ROOT/bench.py --full --steps 3 --warmup 1 --spinup 0 --no-cpu-baseline --no-extras "$@" \
       > $OUT/p$i.log 2>&1
   rc=$?
   echo "== pass $i rc=$rc"

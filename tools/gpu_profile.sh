@@ -4,6 +4,7 @@
 # and the PMC passes that profiles/traffic.json and the VALU counts come from (one counter group
 # per run, as MI355X_MICROARCH.md prescribes).  Usage: tools/gpu_profile.sh <tag>
 set -u
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 TAG=${1:-prof}; OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
 run() {  # name timeout cmd...
@@ -15,13 +16,13 @@ run() {  # name timeout cmd...
   [ $rc -eq 0 ] || exit $rc
 }
 cd $GRAFT_REPO_ROOT
-run bench_c2 300 python bench.py --steps 20 --warmup 3 --e2e
+run bench_c2 300 python bench.py --full --steps 20 --warmup 3 --e2e
 run bench_c3 200 python bench.py --workload c3 --steps 10 --warmup 2 --no-cpu-baseline
 run bench_c5 200 python bench.py --workload c5 --steps 20 --warmup 3 --no-cpu-baseline
 run bench_c5_8m 300 python bench.py --workload c5 --ncw 8388608 --steps 10 --warmup 2 --no-cpu-baseline
 run bench_shards 300 python bench.py --workload shards --steps 10 --warmup 2 --no-cpu-baseline
 cd /tmp
-B="python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-extras"
+B="python3 $ROOT/bench.py --full --no-cpu-baseline --no-extras"
 run prof_c2 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_c2 -o run -- $B --steps 5 --warmup 1
 run prof_c3 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_c3 -o run -- $B --workload c3 --steps 3 --warmup 1
 run prof_c5 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_c5 -o run -- $B --workload c5 --steps 3 --warmup 1

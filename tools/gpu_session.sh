@@ -19,7 +19,7 @@ for v in $VARS; do
 done
 for v in default $VARS; do
   if [ $v = default ]; then unset EZRS_LIB_VARIANT; else export EZRS_LIB_VARIANT=$GRAFT_REPO_ROOT/tools/variants/libezrs_$v.so; fi
-  timeout -k 10 200 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras > $OUT/bench_$v.json 2> $OUT/bench_$v.err
+  timeout -k 10 200 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extras > $OUT/bench_$v.json 2> $OUT/bench_$v.err
   rc=$?; [ $rc -eq 0 ] || { echo "bench $v rc=$rc"; tail -3 $OUT/bench_$v.err; exit $rc; }
   python3 -c "
 import json; d=json.loads(open('$OUT/bench_$v.json').read().splitlines()[-1])

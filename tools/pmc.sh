@@ -18,7 +18,7 @@ i=0
 for grp in "${PMC_SETS[@]}"; do
   i=$((i+1))
   echo "== pmc pass $i: $grp"
-  timeout -k 10 240 rocprofv3 --pmc $grp --output-format csv -d $OUT/p$i -o run -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline "$@" > $OUT/p$i.log 2>&1
+  timeout -k 10 240 rocprofv3 --pmc $grp --output-format csv -d $OUT/p$i -o run -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline "$@" > $OUT/p$i.log 2>&1
   rc=$?
   echo "== pass $i rc=$rc"
   if [ $rc -ne 0 ]; then tail -5 $OUT/p$i.log; echo "stopping"; exit $rc; fi
