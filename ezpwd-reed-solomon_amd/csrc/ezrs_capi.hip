@@ -558,6 +558,176 @@ int ezrs_decode_shards(const ezrs_codec *c, void *shards, size_t shard_pitch, si
     return 0;
 }
 
+// ---- interleaved frames ------------------------------------------------------------------------
+namespace {
+
+// Codewords staged per pass: whole tiles whose staged rows stay well inside the 256 MiB Infinity
+// Cache (EZRS_IL_STAGE_MB, default 64; 0 = the whole batch in one pass, for A/B measurements),
+// capped by the launch_rows test hook rounded up to whole tiles.
+size_t il_chunk_rows(const ezrs_codec *c, unsigned len, size_t ncw) {
+    const size_t w = c->dev.mm <= 8 ? 1 : 2, row = ((size_t)len + c->dev.nroots) * w;
+    size_t n = ncw < kIlMaxRows ? ncw : kIlMaxRows;
+    const char *e = getenv("EZRS_IL_STAGE_MB");
+    const size_t mb = e ? (size_t)strtoull(e, nullptr, 10) : 64;
+    if (mb) {
+        size_t by = (mb << 20) / row / kIlTile * kIlTile;
+        if (by < kIlTile) by = kIlTile;
+        if (by < n) n = by;
+    }
+    if (c->dev.launch_rows) {
+        const size_t lr = (c->dev.launch_rows + kIlTile - 1) / kIlTile * kIlTile;
+        if (lr < n) n = lr;
+    }
+    if (n < ncw) {                                  // equal passes: no short last one
+        const size_t passes = (ncw + n - 1) / n;
+        n = ((ncw + passes - 1) / passes + kIlTile - 1) / kIlTile * kIlTile;
+    }
+    return n;
+}
+
+// Workspace of an interleaved call: the codec's own region for one pass, then the staged rows.
+size_t il_ws_codec(const ezrs_codec *c, size_t chunk) { return (ws_bytes_for(c, chunk) + 255) & ~(size_t)255; }
+size_t il_ws_bytes(const ezrs_codec *c, unsigned len, size_t ncw) {
+    const size_t w = c->dev.mm <= 8 ? 1 : 2, chunk = il_chunk_rows(c, len, ncw);
+    return il_ws_codec(c, chunk) + il_stage_bytes(chunk, (size_t)len + c->dev.nroots, w);
+}
+
+// Argument checks shared by the interleaved calls; ncw = nframes * depth.
+int il_check(const ezrs_codec *c, const void *frames, size_t frame_pitch, size_t sym_stride,
+             size_t depth, unsigned len, size_t nframes, size_t &ncw) {
+    if (!c || !frames || depth == 0 || sym_stride < depth) return -EINVAL;
+    if (len < 1 || len > c->dev.load) return -EINVAL;
+    const size_t ns = (size_t)len + c->dev.nroots;
+    if (nframes > 1 && frame_pitch < (ns - 1) * sym_stride + depth) return -EINVAL;
+    if (depth > SIZE_MAX / nframes) return -EINVAL;
+    ncw = depth * nframes;
+    return 0;
+}
+
+struct IlDecode {
+    const uint32_t *eras;
+    size_t eras_stride;
+    const uint32_t *neras;
+    int32_t *result;
+    uint32_t *positions;
+    size_t pos_stride;
+    void *corr;
+    size_t corr_stride;
+};
+
+// Both directions, pass by pass: gather, the codec's row kernels on the staged rows, scatter.
+//   encode (dec == null): gather the data symbols, scatter the parity symbols of every codeword
+//   decode: gather whole codewords, scatter whole rows of the codewords whose result is nonzero
+int il_run(const ezrs_codec *c, void *frames, size_t frame_pitch, size_t sym_stride, size_t depth,
+           unsigned len, size_t ncw, const IlDecode *dec, void *ws, size_t ws_bytes, void *stream) {
+    if (ws_bytes < il_ws_bytes(c, len, ncw) || !ws) return -EINVAL;
+    DeviceGuard g(c->device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const unsigned NR = c->dev.nroots;
+    const size_t w = c->dev.mm <= 8 ? 1 : 2, P = (size_t)len + NR;
+    const size_t chunk = il_chunk_rows(c, len, ncw);
+    if (ncw == depth) frame_pitch = 0;              // one frame: its pitch is not used
+    char *stage =static_cast<char *>(ws) + il_ws_codec(c, chunk);
+    for (size_t k0 = 0; k0 < ncw; k0 += chunk) {
+        const size_t n = ncw - k0 < chunk ? ncw - k0 : chunk;
+        IlArgs a{frames, frame_pitch, sym_stride, depth, stage, P, k0, (uint32_t)n, 0, dec ? len + NR : len,
+                 nullptr};
+        hipError_t e = launch_il_gather(c->dev, a, st);
+        if (e != hipSuccess) return hip_fail(e, "interleaved gather launch");
+        if (!dec) {
+            EncodeArgs ea{stage, P, len, stage + (size_t)len * w, P, n};
+            if ((e = dispatch_encode(c, ea, ws, st)) != hipSuccess) return hip_fail(e, "encode launch");
+            a.s0 = len;
+            a.s1 = len + NR;
+        } else {
+            DecodeArgs da{stage, P, len, stage + (size_t)len * w, P,
+                          dec->eras ? dec->eras + k0 * dec->eras_stride : nullptr, dec->eras_stride,
+                          dec->neras ? dec->neras + k0 : nullptr, dec->result + k0,
+                          dec->positions ? dec->positions + k0 * dec->pos_stride : nullptr, dec->pos_stride,
+                          dec->corr ? static_cast<char *>(dec->corr) + k0 * dec->corr_stride * w : nullptr,
+                          dec->corr_stride, n};
+            if ((e = dispatch_decode(c, da, static_cast<uint8_t *>(ws), st)) != hipSuccess)
+                return hip_fail(e, "decode launch");
+            a.result = dec->result + k0;
+        }
+        if ((e = launch_il_scatter(c->dev, a, st)) != hipSuccess) return hip_fail(e, "interleaved scatter launch");
+    }
+    return 0;
+}
+
+int il_check_decode(const ezrs_codec *c, size_t ncw, const IlDecode &d) {
+    const unsigned NR = c->dev.nroots;
+    if (!d.result) return -EINVAL;
+    if (d.neras && !d.eras) return -EINVAL;
+    if (d.eras && ncw > 1 && d.eras_stride == 0) return -EINVAL;
+    if (d.positions && ncw > 1 && d.pos_stride < NR) return -EINVAL;
+    if (d.corr && ncw > 1 && d.corr_stride < NR) return -EINVAL;
+    return 0;
+}
+
+} // namespace
+
+size_t ezrs_interleaved_workspace_bytes(const ezrs_codec *c, unsigned len, size_t depth, size_t nframes) {
+    if (!c || len < 1 || len > c->dev.load || depth == 0 || nframes == 0 || depth > SIZE_MAX / nframes)
+        return 0;
+    return il_ws_bytes(c, len, depth * nframes);
+}
+
+int ezrs_encode_interleaved_ws(const ezrs_codec *c, void *frames, size_t frame_pitch, size_t sym_stride,
+                               size_t depth, unsigned len, size_t nframes, void *ws, size_t ws_bytes,
+                               void *stream) {
+    if (!c) return -EINVAL;
+    if (nframes == 0) return 0;
+    size_t ncw;
+    if (int r = il_check(c, frames, frame_pitch, sym_stride, depth, len, nframes, ncw)) return r;
+    return il_run(c, frames, frame_pitch, sym_stride, depth, len, ncw, nullptr, ws, ws_bytes, stream);
+}
+
+int ezrs_encode_interleaved(const ezrs_codec *c, void *frames, size_t frame_pitch, size_t sym_stride,
+                            size_t depth, unsigned len, size_t nframes, void *stream) {
+    if (!c) return -EINVAL;
+    if (nframes == 0) return 0;
+    size_t ncw;
+    if (int r = il_check(c, frames, frame_pitch, sym_stride, depth, len, nframes, ncw)) return r;
+    DeviceGuard g(c->device);
+    const size_t need = il_ws_bytes(c, len, ncw);
+    void *ws = nullptr;
+    if (int r = stream_ws(c, stream, need, &ws)) return r;
+    return il_run(c, frames, frame_pitch, sym_stride, depth, len, ncw, nullptr, ws, need, stream);
+}
+
+int ezrs_decode_interleaved_ws(const ezrs_codec *c, void *frames, size_t frame_pitch, size_t sym_stride,
+                               size_t depth, unsigned len, size_t nframes, const uint32_t *eras,
+                               size_t eras_stride, const uint32_t *neras, int32_t *result,
+                               uint32_t *positions, size_t pos_stride, void *corr, size_t corr_stride,
+                               void *ws, size_t ws_bytes, void *stream) {
+    if (!c) return -EINVAL;
+    if (nframes == 0) return 0;
+    size_t ncw;
+    if (int r = il_check(c, frames, frame_pitch, sym_stride, depth, len, nframes, ncw)) return r;
+    const IlDecode d{eras, eras_stride, neras, result, positions, pos_stride, corr, corr_stride};
+    if (int r = il_check_decode(c, ncw, d)) return r;
+    return il_run(c, frames, frame_pitch, sym_stride, depth, len, ncw, &d, ws, ws_bytes, stream);
+}
+
+int ezrs_decode_interleaved(const ezrs_codec *c, void *frames, size_t frame_pitch, size_t sym_stride,
+                            size_t depth, unsigned len, size_t nframes, const uint32_t *eras,
+                            size_t eras_stride, const uint32_t *neras, int32_t *result,
+                            uint32_t *positions, size_t pos_stride, void *corr, size_t corr_stride,
+                            void *stream) {
+    if (!c) return -EINVAL;
+    if (nframes == 0) return 0;
+    size_t ncw;
+    if (int r = il_check(c, frames, frame_pitch, sym_stride, depth, len, nframes, ncw)) return r;
+    const IlDecode d{eras, eras_stride, neras, result, positions, pos_stride, corr, corr_stride};
+    if (int r = il_check_decode(c, ncw, d)) return r;
+    DeviceGuard g(c->device);
+    const size_t need = il_ws_bytes(c, len, ncw);
+    void *ws = nullptr;
+    if (int r = stream_ws(c, stream, need, &ws)) return r;
+    return il_run(c, frames, frame_pitch, sym_stride, depth, len, ncw, &d, ws, need, stream);
+}
+
 // ---- host-memory pipeline ---------------------------------------------------------------------
 namespace {
 

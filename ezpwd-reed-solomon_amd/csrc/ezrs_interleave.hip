@@ -1,0 +1,265 @@
+// ezrs_interleave.hip -- interleaved frames <-> packed rows (ezrs_encode_interleaved /
+// ezrs_decode_interleaved, include/ezrs.h).
+//
+// A frame carries `depth` codewords interleaved symbol by symbol (CCSDS depth I; striped shards:
+// depth = shard length, symbol stride = shard pitch).  The row kernels want one codeword per row,
+// so k_il_gather copies the frames' symbols into packed rows in a staging area and k_il_scatter
+// copies rows back; the codec's own kernels run unchanged in between (ezrs_capi.hip).
+//
+// Shape of both kernels: a workgroup owns a tile of 256 consecutive codewords (k = f * depth + j),
+// whose staged rows are one contiguous span, and streams over the symbols in chunks of 128 bytes
+// per row through an LDS tile [256 rows][132 bytes].
+//   frame side  lanes are split between consecutive codewords (contiguous along j in a frame) and
+//               consecutive symbols (contiguous too when sym_stride == depth is small): 64 / LS
+//               lanes along j, LS along s, LS chosen per call from the depth, so a wavefront's
+//               accesses fall in few cache lines at every depth.
+//               General path: one element per lane and access, any geometry.
+//               Fast path (uint8_t; depth, sym_stride, frame_pitch and the base multiples of 4): a
+//               lane moves dwords -- four codewords of one symbol -- for four symbols and does the
+//               4x4 byte transpose in registers, so LDS sees dwords only.
+//   row side    consecutive lanes take consecutive 16-byte aligned slots of the rows' span: one
+//               16-byte global access each, aligned dword LDS accesses and a v_alignbyte funnel
+//               shift in between (packed rows start at every byte alignment); the partial slots
+//               at a row segment's two ends are stored from the same registers as dwords and
+//               bytes.
+// LDS pitch 132 bytes = 33 dwords (banks are (a/4) mod 32 for ds_write and ds_read_b32): a column
+// of dwords over consecutive rows, and a row's consecutive dwords, both fall in distinct banks;
+// fast-path frame-side accesses (row 4q + i, dword c) are conflict-free for LS = 4 and 32 and at
+// most 2-way (free on ds_write_b32) for LS = 8 and 16; the row side's 4 rows x 8 slots per
+// 32-lane group are distinct up to each row's alignment shift (at most 2-way).
+// The only division is one per thread and tile (k -> frame, column), 32-bit when it fits.
+#include "ezrs_internal.hpp"
+
+namespace ezrs {
+namespace il {
+
+constexpr unsigned kTile = (unsigned)kIlTile;
+constexpr unsigned kChunkB = 128;             // bytes of a row per symbol chunk
+constexpr unsigned kPitchB = 132;             // LDS row pitch
+constexpr unsigned kSlots = kChunkB / 16 + 1; // 16-byte global slots a row segment can touch
+
+// 4x4 byte transpose: out[t] byte k = in[k] byte t.
+__device__ __forceinline__ void transpose4x4(const uint32_t (&a)[4], uint32_t (&out)[4]) {
+    const uint32_t t01 = __builtin_amdgcn_perm(a[1], a[0], 0x05010400u);
+    const uint32_t t23 = __builtin_amdgcn_perm(a[3], a[2], 0x05010400u);
+    const uint32_t u01 = __builtin_amdgcn_perm(a[1], a[0], 0x07030602u);
+    const uint32_t u23 = __builtin_amdgcn_perm(a[3], a[2], 0x07030602u);
+    out[0] = __builtin_amdgcn_perm(t23, t01, 0x05040100u);
+    out[1] = __builtin_amdgcn_perm(t23, t01, 0x07060302u);
+    out[2] = __builtin_amdgcn_perm(u23, u01, 0x05040100u);
+    out[3] = __builtin_amdgcn_perm(u23, u01, 0x07060302u);
+}
+
+// Element offset of codeword k's symbol 0 in the frames.
+__device__ __forceinline__ size_t frame_off(const IlArgs &a, size_t k) {
+    size_t f, j;
+    if (((k | a.depth) >> 32) == 0) {               // 32-bit division (see shard_row)
+        const uint32_t k32 = (uint32_t)k, d32 = (uint32_t)a.depth, f32 = k32 / d32;
+        f = f32;
+        j = k32 - f32 * d32;
+    } else {
+        f = k / a.depth;
+        j = k - f * a.depth;
+    }
+    return f * a.frame_pitch + j;
+}
+
+// Frames -> rows.  lg = log2(LS).
+template <typename T, bool FAST>
+__global__ void __launch_bounds__(256) k_il_gather(IlArgs a, unsigned lg) {
+    // 16 guard bytes on either side: a partial slot's aligned dword reads may start before row 0
+    // and end after row 255 (those bytes are never stored)
+    __shared__ __attribute__((aligned(16))) uint8_t lds[16 + kTile * kPitchB + 16];
+    __shared__ size_t off[kTile];
+    uint8_t *const tile = lds + 16;
+    constexpr unsigned SC = kChunkB / sizeof(T), PT = kPitchB / sizeof(T);
+    const unsigned t = threadIdx.x;
+    const size_t kt0 = (size_t)blockIdx.x * kTile;
+    const unsigned nk = a.n - kt0 < kTile ? (unsigned)(a.n - kt0) : kTile;
+    off[t] = t < nk ? frame_off(a, a.k0 + kt0 + t) : 0;
+    const T *frames = static_cast<const T *>(a.frames);
+    uint8_t *rb = static_cast<uint8_t *>(a.rows);
+    const unsigned ls = 1u << lg, si = t & (ls - 1), ki = t >> lg, kstep = 256u >> lg;
+    for (unsigned sa = a.s0; sa < a.s1; sa += SC) {
+        const unsigned ns = a.s1 - sa < SC ? a.s1 - sa : SC;
+        __syncthreads();                            // off[] written; the tile's last chunk stored
+        if constexpr (FAST) {
+#pragma unroll 4
+            for (unsigned q = ki; 4 * q < nk; q += kstep) {
+                const uint8_t *p = reinterpret_cast<const uint8_t *>(frames) + off[4 * q] + (size_t)sa * a.sym_stride;
+                for (unsigned s4 = 4 * si; s4 < ns; s4 += 4 * ls) {
+                    uint32_t in[4], out[4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        in[i] = s4 + i < ns ? *reinterpret_cast<const uint32_t *>(p + (size_t)(s4 + i) * a.sym_stride) : 0u;
+                    transpose4x4(in, out);          // out[i]: symbols s4..s4+3 of codeword 4q + i
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        *reinterpret_cast<uint32_t *>(tile + (4 * q + i) * kPitchB + s4) = out[i];
+                }
+            }
+        } else {
+            T *lt = reinterpret_cast<T *>(tile);
+            for (unsigned kk = ki; kk < nk; kk += kstep) {
+                const T *p = frames + off[kk] + (size_t)sa * a.sym_stride;
+#pragma unroll 8
+                for (unsigned s = si; s < ns; s += ls) lt[kk * PT + s] = p[(size_t)s * a.sym_stride];
+            }
+        }
+        __syncthreads();
+        // rows: the 16-byte aligned slots of every row's segment [g, g + nb)
+        const unsigned nb = ns * (unsigned)sizeof(T);
+        for (unsigned e = t; e < nk * kSlots; e += 256) {
+            const unsigned kk = e / kSlots, q = e - kk * kSlots;
+            const size_t g = ((kt0 + kk) * a.row_pitch + sa) * sizeof(T);
+            const size_t G = (g & ~(size_t)15) + 16 * q;
+            const int d = (int)(ptrdiff_t)(G - g);                 // -15 .. 128
+            if (d >= (int)nb) continue;
+            // bytes d .. d + 15 of the row's LDS segment from aligned dwords (d < 0 or d + 16 > nb:
+            // the out-of-segment bytes come from the neighbouring rows or the guards and are dropped)
+            const uint32_t *lw = reinterpret_cast<const uint32_t *>(tile + kk * kPitchB + (d & ~3));
+            const uint32_t r = (uint32_t)d & 3;
+            const uint32_t w0 = lw[0], w1 = lw[1], w2 = lw[2], w3 = lw[3], w4 = lw[4];
+            const uint32_t o[4] = {__builtin_amdgcn_alignbyte(w1, w0, r), __builtin_amdgcn_alignbyte(w2, w1, r),
+                                   __builtin_amdgcn_alignbyte(w3, w2, r), __builtin_amdgcn_alignbyte(w4, w3, r)};
+            if (d >= 0 && d + 16 <= (int)nb) {
+                *reinterpret_cast<uint4 *>(rb + G) = make_uint4(o[0], o[1], o[2], o[3]);
+            } else {                                // a segment's first or last slot: dwords, then bytes
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int p0 = d + 4 * i;
+                    if (p0 >= 0 && p0 + 4 <= (int)nb) {
+                        *reinterpret_cast<uint32_t *>(rb + G + 4 * i) = o[i];
+                    } else {
+#pragma unroll
+                        for (int b = 0; b < 4; ++b)
+                            if (p0 + b >= 0 && p0 + b < (int)nb) rb[G + 4 * i + b] = (uint8_t)(o[i] >> (8 * b));
+                    }
+                }
+            }
+        }
+    }
+}
+
+// Rows -> frames, for every codeword of the tile (result == null) or those with a nonzero result.
+template <typename T, bool FAST>
+__global__ void __launch_bounds__(256) k_il_scatter(IlArgs a, unsigned lg) {
+    __shared__ __attribute__((aligned(16))) uint8_t tile[kTile * kPitchB];
+    __shared__ size_t off[kTile];
+    __shared__ __attribute__((aligned(4))) uint8_t flag[kTile];   // 1: write this codeword back
+    constexpr unsigned SC = kChunkB / sizeof(T), PT = kPitchB / sizeof(T);
+    const unsigned t = threadIdx.x;
+    const size_t kt0 = (size_t)blockIdx.x * kTile;
+    const unsigned nk = a.n - kt0 < kTile ? (unsigned)(a.n - kt0) : kTile;
+    const bool mine = t < nk && (!a.result || a.result[kt0 + t] != 0);
+    flag[t] = mine;
+    if (!__syncthreads_or(mine)) return;            // a tile of clean codewords: nothing to write
+    off[t] = mine ? frame_off(a, a.k0 + kt0 + t) : 0;
+    T *frames = static_cast<T *>(a.frames);
+    const uint8_t *rb = static_cast<const uint8_t *>(a.rows);
+    const unsigned ls = 1u << lg, si = t & (ls - 1), ki = t >> lg, kstep = 256u >> lg;
+    for (unsigned sa = a.s0; sa < a.s1; sa += SC) {
+        const unsigned ns = a.s1 - sa < SC ? a.s1 - sa : SC;
+        const unsigned nb = ns * (unsigned)sizeof(T);
+        __syncthreads();
+        // rows -> LDS: 16-byte LDS slots from aligned global dwords (reads may run up to 19 bytes
+        // past the segment: inside the staging area, il_stage_bytes)
+        for (unsigned e = t; e < nk * (kChunkB / 16); e += 256) {
+            const unsigned kk = e >> 3, q = e & 7;
+            if (16 * q >= nb || !flag[kk]) continue;
+            const size_t g = ((kt0 + kk) * a.row_pitch + sa) * sizeof(T) + 16 * q;
+            const uint32_t *gp = reinterpret_cast<const uint32_t *>(rb + (g & ~(size_t)3));
+            const uint32_t r = (uint32_t)g & 3;
+            const uint32_t w0 = gp[0], w1 = gp[1], w2 = gp[2], w3 = gp[3], w4 = r ? gp[4] : 0u;
+            uint32_t *lw = reinterpret_cast<uint32_t *>(tile + kk * kPitchB + 16 * q);
+            lw[0] = __builtin_amdgcn_alignbyte(w1, w0, r);
+            lw[1] = __builtin_amdgcn_alignbyte(w2, w1, r);
+            lw[2] = __builtin_amdgcn_alignbyte(w3, w2, r);
+            lw[3] = __builtin_amdgcn_alignbyte(w4, w3, r);
+        }
+        __syncthreads();
+        if constexpr (FAST) {
+            for (unsigned q = ki; 4 * q < nk; q += kstep) {
+                const uint32_t fl = *reinterpret_cast<const uint32_t *>(flag + 4 * q);
+                if (!fl) continue;
+                // off[] of the quad's first flagged codeword gives the quad's base
+                const unsigned i0 = (fl & 0xFFu) ? 0 : (fl & 0xFF00u) ? 1 : (fl & 0xFF0000u) ? 2 : 3;
+                uint8_t *p = reinterpret_cast<uint8_t *>(frames) + (off[4 * q + i0] - i0) + (size_t)sa * a.sym_stride;
+                for (unsigned s4 = 4 * si; s4 < ns; s4 += 4 * ls) {
+                    uint32_t in[4], out[4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        in[i] = *reinterpret_cast<const uint32_t *>(tile + (4 * q + i) * kPitchB + s4);
+                    transpose4x4(in, out);          // out[m]: symbol s4 + m of codewords 4q..4q+3
+#pragma unroll
+                    for (int m = 0; m < 4; ++m) {
+                        if (s4 + m >= ns) continue;
+                        uint8_t *dst = p + (size_t)(s4 + m) * a.sym_stride;
+                        if (fl == 0x01010101u) {
+                            *reinterpret_cast<uint32_t *>(dst) = out[m];
+                        } else {
+#pragma unroll
+                            for (int b = 0; b < 4; ++b)
+                                if ((fl >> (8 * b)) & 0xFFu) dst[b] = (uint8_t)(out[m] >> (8 * b));
+                        }
+                    }
+                }
+            }
+        } else {
+            const T *lt = reinterpret_cast<const T *>(tile);
+            for (unsigned kk = ki; kk < nk; kk += kstep) {
+                if (!flag[kk]) continue;
+                T *p = frames + off[kk] + (size_t)sa * a.sym_stride;
+#pragma unroll 4
+                for (unsigned s = si; s < ns; s += ls) p[(size_t)s * a.sym_stride] = lt[kk * PT + s];
+            }
+        }
+    }
+}
+
+// Fast path: uint8_t, every dword of four codewords aligned.
+static bool fast_ok(const DevCodec &d, const IlArgs &a) {
+    if (d.mm > 8) return false;
+    return ((a.depth | a.sym_stride | a.frame_pitch | (size_t)(uintptr_t)a.frames) & 3) == 0;
+}
+
+// log2 of the lanes along the symbols: the others (64 / LS) go along j, as many as one frame has
+// consecutive codewords (fast path: dwords of four) to give, rounded down to a power of two.
+static unsigned lanes_log2(size_t depth, bool fast) {
+    const size_t per = fast ? depth / 4 : depth;
+    unsigned lj = 0;                                // log2 of the lanes along j
+    while (lj < 6 && ((size_t)2 << lj) <= per) ++lj;
+    unsigned lg = 6 - lj;
+    if (fast) {                                     // 4..32: the LDS bank analysis above
+        if (lg < 2) lg = 2;
+        if (lg > 5) lg = 5;
+    }
+    return lg;
+}
+
+template <bool GATHER>
+static hipError_t launch(const DevCodec &d, const IlArgs &a, hipStream_t s) {
+    if (!a.n || a.s0 >= a.s1) return hipSuccess;
+    if (a.n > kIlMaxRows) return hipErrorInvalidValue;
+    const bool fast = fast_ok(d, a);
+    const unsigned lg = lanes_log2(a.depth, fast);
+    const dim3 grid((unsigned)((a.n + kTile - 1) / kTile)), block(256);
+    if (d.mm > 8) {
+        if (GATHER) hipLaunchKernelGGL((k_il_gather<uint16_t, false>), grid, block, 0, s, a, lg);
+        else hipLaunchKernelGGL((k_il_scatter<uint16_t, false>), grid, block, 0, s, a, lg);
+    } else if (fast) {
+        if (GATHER) hipLaunchKernelGGL((k_il_gather<uint8_t, true>), grid, block, 0, s, a, lg);
+        else hipLaunchKernelGGL((k_il_scatter<uint8_t, true>), grid, block, 0, s, a, lg);
+    } else {
+        if (GATHER) hipLaunchKernelGGL((k_il_gather<uint8_t, false>), grid, block, 0, s, a, lg);
+        else hipLaunchKernelGGL((k_il_scatter<uint8_t, false>), grid, block, 0, s, a, lg);
+    }
+    return hipGetLastError();
+}
+
+} // namespace il
+
+hipError_t launch_il_gather(const DevCodec &d, const IlArgs &a, hipStream_t s) { return il::launch<true>(d, a, s); }
+hipError_t launch_il_scatter(const DevCodec &d, const IlArgs &a, hipStream_t s) { return il::launch<false>(d, a, s); }
+
+} // namespace ezrs

@@ -166,4 +166,29 @@ hipError_t launch_wide_encode(int id, const DevCodec &d, const EncodeArgs &a, co
 hipError_t launch_wide_decode(int id, const DevCodec &d, const DecodeArgs &a, const uint16_t *blob_host,
                               const uint16_t *cols_dev, void *ws, hipStream_t s);
 
+// Interleaved frames (ezrs_interleave.hip; ezrs_encode_interleaved / ezrs_decode_interleaved):
+// symbol s of codeword k = f * depth + j is element f * frame_pitch + s * sym_stride + j of
+// `frames`.  The kernels copy symbols [s0, s1) of codewords k0 .. k0 + n - 1 between the frames and
+// packed rows (row k - k0 at rows + (k - k0) * row_pitch, symbol s at column s), so the row kernels
+// run unchanged on the staged rows.  Elements are the codec's datum; strides in elements.
+struct IlArgs {
+    void *frames;
+    size_t frame_pitch, sym_stride, depth;
+    void *rows;                   // 16-byte aligned; il_stage_bytes() bytes
+    size_t row_pitch;
+    size_t k0;                    // first codeword (frame-major index over the whole batch)
+    uint32_t n;                   // codewords (<= kIlMaxRows)
+    uint32_t s0, s1;              // symbols to copy
+    const int32_t *result;        // scatter: null = every codeword, else only those with
+                                  // result[k - k0] != 0 (the others are never written)
+};
+constexpr size_t kIlTile = 256;                   // codewords per workgroup (the row kernels' tile)
+constexpr size_t kIlMaxRows = (size_t)1 << 31;    // per launch
+// Staging bytes of n rows (the scatter's aligned dword loads may read a few bytes past the last row).
+inline size_t il_stage_bytes(size_t n, size_t row_pitch, size_t w) {
+    return (n * row_pitch * w + 32 + 255) & ~(size_t)255;
+}
+hipError_t launch_il_gather(const DevCodec &d, const IlArgs &a, hipStream_t s);
+hipError_t launch_il_scatter(const DevCodec &d, const IlArgs &a, hipStream_t s);
+
 } // namespace ezrs

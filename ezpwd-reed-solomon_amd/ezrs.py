@@ -92,6 +92,14 @@ def lib():
         L.ezrs_encode_shards.argtypes = [_vp, _vp, _sz, _sz, _u, _sz, _vp]
         L.ezrs_decode_shards.argtypes = [_vp, _vp, _sz, _sz, _u, _sz, _vp, _sz, _vp, _vp, _vp, _sz,
                                          _vp, _sz, _vp]
+        L.ezrs_interleaved_workspace_bytes.restype = _sz
+        L.ezrs_interleaved_workspace_bytes.argtypes = [_vp, _u, _sz, _sz]
+        L.ezrs_encode_interleaved.argtypes = [_vp, _vp, _sz, _sz, _sz, _u, _sz, _vp]
+        L.ezrs_encode_interleaved_ws.argtypes = [_vp, _vp, _sz, _sz, _sz, _u, _sz, _vp, _sz, _vp]
+        L.ezrs_decode_interleaved.argtypes = [_vp, _vp, _sz, _sz, _sz, _u, _sz, _vp, _sz, _vp, _vp,
+                                              _vp, _sz, _vp, _sz, _vp]
+        L.ezrs_decode_interleaved_ws.argtypes = [_vp, _vp, _sz, _sz, _sz, _u, _sz, _vp, _sz, _vp,
+                                                 _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp]
         L.ezrs_kernel_path.argtypes = [_vp]
         L.ezrs_set_launch_rows.argtypes = [_vp, _sz]
         L.ezrs_set_semantics.argtypes = [_vp, _i]
@@ -327,6 +335,57 @@ class Codec:
         _check(lib().ezrs_decode_shards(
             self._h, _tp(shards), sp, shard_len, chunk, shards.shape[0], _tp(eras), es, _tp(neras),
             _tp(result), _tp(positions), qs, _tp(corr), cs, _stream_ptr(stream)), "ezrs_decode_shards")
+        return result
+
+    # -- interleaved frames (CCSDS depth I, striped shards) ------------------------------------
+    def _frames(self, frames):
+        """Validate a [nframes, len + nroots, depth] device tensor with a contiguous last
+        dimension; returns (frame_pitch, sym_stride, depth, len, nframes)."""
+        w = self.info.datum_bytes
+        if not getattr(frames, "is_cuda", False):
+            raise EzrsError("frames: expected a GPU tensor")
+        if frames.device.index != self.device:
+            raise EzrsError(f"frames: tensor on cuda:{frames.device.index}, codec on cuda:{self.device}")
+        if frames.element_size() != w:
+            raise EzrsError(f"frames: expected {w}-byte elements, got {frames.dtype}")
+        if frames.dim() != 3 or (frames.shape[2] > 1 and frames.stride(2) != 1):
+            raise EzrsError("frames: expected a 3-D tensor [nframes, len + nroots, depth] with a "
+                            "contiguous last dimension")
+        nframes, nsym, depth = frames.shape
+        if nsym <= self.nroots or nsym > self.nn or depth == 0:
+            raise EzrsError(f"frames: {nsym} symbols per codeword, expected {self.nroots + 1}.."
+                            f"{self.nn}, and a depth of at least 1")
+        return frames.stride(0), frames.stride(1), depth, nsym - self.nroots, nframes
+
+    def interleaved_workspace_bytes(self, length, depth, nframes):
+        return int(lib().ezrs_interleaved_workspace_bytes(self._h, length, depth, nframes))
+
+    def encode_interleaved(self, frames, stream=None):
+        """frames: [nframes, len + nroots, depth] device tensor (a CCSDS buffer: buf.view(F, 255, I);
+        a stripe of N shards: shards[None] of a [N, pitch] tensor sliced to [:, :shard_len]); writes
+        the nroots parity symbols of every codeword (ezrs_encode_interleaved)."""
+        fp, ss, depth, length, nframes = self._frames(frames)
+        _check(lib().ezrs_encode_interleaved(self._h, _tp(frames), fp, ss, depth, length, nframes,
+                                             _stream_ptr(stream)), "ezrs_encode_interleaved")
+
+    def decode_interleaved(self, frames, eras=None, neras=None, result=None, positions=None,
+                           corr=None, stream=None):
+        """In-place decode of every codeword of every frame; returns the int32 result tensor
+        [nframes * depth] (frame-major, k = f * depth + j) -- ezrs_decode_interleaved."""
+        import torch
+        w = self.info.datum_bytes
+        fp, ss, depth, length, nframes = self._frames(frames)
+        es = _dev_rows(eras, "eras", self.device, 4)
+        _dev_rows(neras, "neras", self.device, 4, ndim=1)
+        qs = _dev_rows(positions, "positions", self.device, 4)
+        cs = _dev_rows(corr, "corr", self.device, w)
+        if result is None:
+            result = torch.empty(nframes * depth, dtype=torch.int32, device=frames.device)
+        _dev_rows(result, "result", self.device, 4, ndim=1)
+        _check(lib().ezrs_decode_interleaved(
+            self._h, _tp(frames), fp, ss, depth, length, nframes, _tp(eras), es, _tp(neras),
+            _tp(result), _tp(positions), qs, _tp(corr), cs, _stream_ptr(stream)),
+            "ezrs_decode_interleaved")
         return result
 
     # -- host batch forms ----------------------------------------------------------------------

@@ -183,6 +183,50 @@ int ezrs_decode_shards(const ezrs_codec *codec, void *shards, size_t shard_pitch
                        const uint32_t *neras, int32_t *result, uint32_t *positions,
                        size_t pos_stride, void *corr, size_t corr_stride, void *stream);
 
+/* Interleaved frames (device-resident).  A frame carries `depth` codewords interleaved symbol by
+ * symbol: symbol s (0 <= s < len + NROOTS, data first, then parity) of codeword j (0 <= j < depth)
+ * of frame f is element  frames[f*frame_pitch + s*sym_stride + j]  (strides in elements of the
+ * datum).  The reference has no interleaving: each call replaces de-interleaving on the host, the
+ * per-codeword loop of encode / decode calls (rs_base:868-904, 1170-1242) and re-interleaving.
+ *   CCSDS depth I      sym_stride == depth == I, frame_pitch >= (len + NROOTS) * I; a 1275-byte
+ *                      RS_CCSDS(255,223) I = 5 codeblock is one frame.
+ *   striped shards     K data and NROOTS parity shards of shard_len symbols, byte j of every shard
+ *                      forming codeword j: nframes = 1, depth = shard_len, sym_stride = shard pitch
+ *                      (ezrs_*_shards above is the rsencode layout, codewords contiguous in a shard).
+ * Codewords are numbered frame-major, k = f*depth + j: result[k] and the erasure / position /
+ * correction rows k, and positions relative to the codeword's first data symbol, mean what they
+ * mean in ezrs_decode, under both semantics.  len < load is a shortened code.
+ * The frames are gathered into packed rows in the workspace, the codec's row kernels run on those,
+ * and rows are scattered back, a bounded number of codewords per pass.  Encode writes only the
+ * NROOTS parity symbols of every codeword; decode writes only the symbols of codewords whose
+ * result is nonzero (a -1 row carries the reference's partial corrections, rs_base:1610-1690).  No
+ * other element of `frames` is ever written: not the gaps of sym_stride > depth, not the padding
+ * after a frame's last symbol row or between frames.
+ * The *_ws forms take a caller-owned workspace of >= ezrs_interleaved_workspace_bytes() bytes
+ * (which is exactly what a call uses; 0 for invalid arguments) and allocate nothing.
+ * -EINVAL: null codec, frames or result; depth == 0; sym_stride < depth; len outside 1..load;
+ * nframes > 1 with frame_pitch < (len + NROOTS - 1)*sym_stride + depth; the stride rules of
+ * ezrs_decode for eras, positions and corr when the batch has more than one codeword; a workspace
+ * that is too small.  nframes == 0 returns 0 and touches nothing. */
+size_t ezrs_interleaved_workspace_bytes(const ezrs_codec *codec, unsigned len, size_t depth,
+                                        size_t nframes);
+int ezrs_encode_interleaved(const ezrs_codec *codec, void *frames, size_t frame_pitch,
+                            size_t sym_stride, size_t depth, unsigned len, size_t nframes,
+                            void *stream);
+int ezrs_encode_interleaved_ws(const ezrs_codec *codec, void *frames, size_t frame_pitch,
+                               size_t sym_stride, size_t depth, unsigned len, size_t nframes,
+                               void *ws, size_t ws_bytes, void *stream);
+int ezrs_decode_interleaved(const ezrs_codec *codec, void *frames, size_t frame_pitch,
+                            size_t sym_stride, size_t depth, unsigned len, size_t nframes,
+                            const uint32_t *eras, size_t eras_stride, const uint32_t *neras,
+                            int32_t *result, uint32_t *positions, size_t pos_stride, void *corr,
+                            size_t corr_stride, void *stream);
+int ezrs_decode_interleaved_ws(const ezrs_codec *codec, void *frames, size_t frame_pitch,
+                               size_t sym_stride, size_t depth, unsigned len, size_t nframes,
+                               const uint32_t *eras, size_t eras_stride, const uint32_t *neras,
+                               int32_t *result, uint32_t *positions, size_t pos_stride, void *corr,
+                               size_t corr_stride, void *ws, size_t ws_bytes, void *stream);
+
 /* Host-memory forms: the same contracts with HOST pointers.  The batch is streamed through the
  * device in chunks of `chunk` codewords (0 = library default) over two HIP streams with
  * asynchronous copies; pinned host memory (ezrs_host_alloc) gets full PCIe overlap.  Blocking:
