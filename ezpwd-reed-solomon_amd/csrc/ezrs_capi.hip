@@ -52,7 +52,17 @@ struct ezrs_codec {
     mutable std::vector<void *> ws_retired;
 };
 
+// A reconstruction plan: one loss pattern of one codec and length.  It holds copies of what it needs
+// from the codec and is const after ezrs_recon_create.
+struct ezrs_recon {
+    int device = 0;
+    unsigned mm = 0, nroots = 0, len = 0, nlost = 0, nsurv = 0;
+    uint32_t *d_tab = nullptr;    // recon_table
+};
+
 namespace {
+
+constexpr size_t kReconMaxTable = (size_t)64 << 20;   // bytes of a plan's device table (engine limit)
 
 thread_local std::string g_last_error;
 
@@ -726,6 +736,82 @@ int ezrs_decode_interleaved(const ezrs_codec *c, void *frames, size_t frame_pitc
     void *ws = nullptr;
     if (int r = stream_ws(c, stream, need, &ws)) return r;
     return il_run(c, frames, frame_pitch, sym_stride, depth, len, ncw, &d, ws, need, stream);
+}
+
+// ---- shared-erasure reconstruction --------------------------------------------------------------
+int ezrs_recon_create(ezrs_recon **out, const ezrs_codec *c, unsigned len, const uint32_t *lost,
+                      unsigned nlost) {
+    if (!out) return -EINVAL;
+    *out = nullptr;
+    if (!c) return -EINVAL;
+    const CodecMath &m = c->math;
+    if (!recon_check(m, len, lost, nlost)) {
+        g_last_error = "reconstruction plan: len outside 1..load, or lost positions that are not "
+                       "distinct, below len + NROOTS and at most NROOTS";
+        return -EINVAL;
+    }
+    const unsigned NR = m.spec.nroots, nsurv = len + NR - nlost;
+    const size_t words = recon_table_words(m.spec.mm, NR, nsurv, nlost);
+    if (words * sizeof(uint32_t) > kReconMaxTable) {
+        g_last_error = "reconstruction plan: device table above 64 MiB";
+        return -ENOTSUP;
+    }
+    ezrs_recon *p = nullptr;
+    std::vector<uint32_t> tab;
+    try {
+        p = new ezrs_recon;
+        std::vector<uint16_t> cols;
+        std::vector<uint32_t> surv;
+        if (!recon_build(m, len, lost, nlost, cols, surv)) {
+            delete p;
+            return -EINVAL;
+        }
+        recon_table(m.spec.mm, NR, cols, surv, lost, nlost, tab);
+    } catch (const std::bad_alloc &) {
+        delete p;
+        return -ENOMEM;
+    }
+    p->device = c->device;
+    p->mm = m.spec.mm;
+    p->nroots = NR;
+    p->len = len;
+    p->nlost = nlost;
+    p->nsurv = nsurv;
+    DeviceGuard g(c->device);
+    hipError_t e;
+    if ((e = hipMalloc(&p->d_tab, tab.size() * sizeof(uint32_t))) != hipSuccess ||
+        (e = hipMemcpy(p->d_tab, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice)) !=
+            hipSuccess) {
+        ezrs_recon_destroy(p);
+        return hip_fail(e, "hipMalloc(reconstruction table)");
+    }
+    *out = p;
+    return 0;
+}
+
+int ezrs_recon_destroy(ezrs_recon *p) {
+    if (!p) return 0;
+    DeviceGuard g(p->device);
+    if (p->d_tab) (void)hipFree(p->d_tab);
+    delete p;
+    return 0;
+}
+
+int ezrs_reconstruct_interleaved(const ezrs_recon *p, void *frames, size_t frame_pitch, size_t sym_stride,
+                                 size_t depth, size_t nframes, int32_t *result, void *stream) {
+    if (!p) return -EINVAL;
+    if (nframes == 0) return 0;
+    if (!frames || depth == 0 || sym_stride < depth) return -EINVAL;
+    const size_t ns = (size_t)p->len + p->nroots;
+    if (nframes > 1 && frame_pitch < (ns - 1) * sym_stride + depth) return -EINVAL;
+    if (depth > SIZE_MAX / nframes) return -EINVAL;
+    if (nframes == 1) frame_pitch = 0;              // one frame: its pitch is not used
+    DeviceGuard g(p->device);
+    ReconArgs a{frames, frame_pitch, sym_stride, depth, 0, 0, 0, 0, result, p->nsurv, p->nlost, p->mm,
+                recon_row_pad(p->nroots), result ? p->nroots : p->nlost};
+    hipError_t e = launch_recon(a, nframes, p->d_tab, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "reconstruction launch");
+    return 0;
 }
 
 // ---- host-memory pipeline ---------------------------------------------------------------------

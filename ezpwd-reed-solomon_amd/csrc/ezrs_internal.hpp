@@ -191,4 +191,33 @@ inline size_t il_stage_bytes(size_t n, size_t row_pitch, size_t w) {
 hipError_t launch_il_gather(const DevCodec &d, const IlArgs &a, hipStream_t s);
 hipError_t launch_il_scatter(const DevCodec &d, const IlArgs &a, hipStream_t s);
 
+// Shared-erasure reconstruction of interleaved frames (ezrs_recon.hip; ezrs_recon_create /
+// ezrs_reconstruct_interleaved): one constant GF matrix per loss pattern, applied to the survivors
+// in place.  recon_build: the matrix as bit columns, cols[row][survivor][bit] (rows 0..nlost-1
+// rebuild lost[0..nlost-1], the others are check rows), and the surviving positions, ascending;
+// false for a bad length or loss list (recon_check).  recon_table: the device table of a plan,
+// coefficients | survivors | lost | the per-row constant the kernel takes out of its accumulators
+// at the end; coefficients for m > 8: [survivor][bit][recon_row_pad(nroots)] columns replicated
+// across a dword, for m <= 8: [survivor][group of 3 bits][recon_row_pad(nroots)][2] dwords, the
+// images of the group's 8 values as bytes.
+bool recon_check(const CodecMath &m, unsigned len, const uint32_t *lost, unsigned nlost);
+bool recon_build(const CodecMath &m, unsigned len, const uint32_t *lost, unsigned nlost,
+                 std::vector<uint16_t> &cols, std::vector<uint32_t> &surv);
+unsigned recon_row_pad(unsigned nroots);
+size_t recon_table_words(unsigned mm, unsigned nroots, unsigned nsurv, unsigned nlost);
+void recon_table(unsigned mm, unsigned nroots, const std::vector<uint16_t> &cols,
+                 const std::vector<uint32_t> &surv, const uint32_t *lost, unsigned nlost,
+                 std::vector<uint32_t> &tab);
+struct ReconArgs {
+    void *frames;
+    size_t frame_pitch, sym_stride, depth;
+    size_t j0, runs;              // set per launch: first codeword of a frame, lanes per frame
+    size_t f0, nf;                // set per launch: frames
+    int32_t *result;              // nullable
+    unsigned nsurv, nlost, mm;
+    unsigned nrp;                 // recon_row_pad(nroots)
+    unsigned nrows;               // rows to apply: nroots, or nlost when result is null
+};
+hipError_t launch_recon(const ReconArgs &a, size_t nframes, const uint32_t *tab, hipStream_t s);
+
 } // namespace ezrs

@@ -1,0 +1,521 @@
+// ezrs_recon.hip -- shared-erasure reconstruction of interleaved frames (ezrs_recon_create /
+// ezrs_reconstruct_interleaved, include/ezrs.h).
+//
+// Striped shards lose whole shards: every codeword of the stripe has the same erasure positions and
+// no other errors.  The erasure system is then solved once per loss pattern on the host
+// (recon_build) and what is left for the device is one constant matrix over GF(2^m) applied to the
+// surviving symbols of every codeword, in place in the frames: no gather, no staging, no
+// per-codeword control flow.
+//
+// The matrix.  S = len + NROOTS symbols, position p relative to the first data symbol,
+// X(i, p) = alpha^((fcr + i) * prim * (S - 1 - p)), so that syndrome i of a word c is
+// sum_p X(i, p) c_p.  With A = X(i < nlost, lost[r]):
+//   rebuild rows  r < nlost      R[r][c] = sum_i A^-1[r][i] X(i, surv[c])   -> the symbol at lost[r]
+//   check rows    nlost <= i     R[i][c] = X(i, surv[c]) + sum_r X(i, lost[r]) R[r][c]
+//                                                          -> syndrome i of the rebuilt word
+// The kernel never multiplies in the field: a coefficient is kept as its m bit columns in the
+// codec's stored representation, col[r][c][b] = rep(R[r][c] * unrep(1 << b)) (rep / unrep: the CCSDS
+// dual-basis maps, or the identity), and an output symbol is the XOR of the columns of the set bits
+// of the survivors.  That covers every m and the dual basis with no table of the field.
+//
+// The kernel.  A lane owns a run of consecutive codewords of one frame: 16 bytes (one dwordx4 per
+// symbol row) when the base and the strides allow it, else a dword, else one element; consecutive
+// lanes take consecutive runs, so every survivor load and every lost-symbol store is coalesced.
+//   m > 8   bit-column form (apply): per survivor dword and bit b the SWAR mask of the codewords
+//           whose bit b is set is formed once and shared by all rows: acc[row] ^= mask & K[row][c][b]
+//           (one v_bitop3), K being the bit column replicated across the dword.
+//   m <= 8  byte form (apply8, apply8x2): the columns of three bits are folded on the host into an
+//           8-entry byte table per row, and v_perm_b32 looks up the four codewords of a dword at
+//           once: three lookups per row and dword instead of eight mask-and-XOR steps.
+// The tables are indexed with wave-uniform values only and come through the scalar cache.  Rows
+// are taken RB at a time (RB accumulators per dword of the run); the blocks of a plan with more
+// rows are looped inside the kernel, so the check rows of all blocks are OR-ed in registers and
+// `result` is written once, whatever the order.
+#include <algorithm>
+#include <cerrno>
+#include <new>
+#include <utility>
+
+#include "../../include/ezrs.h"
+#include "ezrs_internal.hpp"
+
+namespace ezrs {
+
+namespace {
+
+// alpha^((fcr + i) * prim * (S - 1 - p))
+inline unsigned recon_x(const CodecMath &m, unsigned i, unsigned S, unsigned p) {
+    const uint64_t root = ((uint64_t)m.spec.fcr + i) % m.nn * (m.spec.prim % m.nn) % m.nn;
+    return m.gf.alpha_to[root * (S - 1 - p) % m.nn];
+}
+
+inline unsigned gf_inv(const Field &gf, unsigned a) { return gf.alpha_to[(gf.nn - gf.index_of[a]) % gf.nn]; }
+
+// In-place Gauss-Jordan inverse of the n x n matrix a (row-major); false if singular.
+bool gf_invert(const Field &gf, std::vector<uint16_t> &a, unsigned n) {
+    std::vector<uint16_t> inv((size_t)n * n, 0);
+    for (unsigned i = 0; i < n; ++i) inv[(size_t)i * n + i] = 1;
+    for (unsigned col = 0; col < n; ++col) {
+        unsigned piv = col;
+        while (piv < n && !a[(size_t)piv * n + col]) ++piv;
+        if (piv == n) return false;
+        if (piv != col)
+            for (unsigned j = 0; j < n; ++j) {
+                std::swap(a[(size_t)piv * n + j], a[(size_t)col * n + j]);
+                std::swap(inv[(size_t)piv * n + j], inv[(size_t)col * n + j]);
+            }
+        const unsigned s = gf_inv(gf, a[(size_t)col * n + col]);
+        for (unsigned j = 0; j < n; ++j) {
+            a[(size_t)col * n + j] = (uint16_t)gf.mul(a[(size_t)col * n + j], s);
+            inv[(size_t)col * n + j] = (uint16_t)gf.mul(inv[(size_t)col * n + j], s);
+        }
+        for (unsigned r = 0; r < n; ++r) {
+            const unsigned f = a[(size_t)r * n + col];
+            if (r == col || !f) continue;
+            for (unsigned j = 0; j < n; ++j) {
+                a[(size_t)r * n + j] ^= (uint16_t)gf.mul(a[(size_t)col * n + j], f);
+                inv[(size_t)r * n + j] ^= (uint16_t)gf.mul(inv[(size_t)col * n + j], f);
+            }
+        }
+    }
+    a.swap(inv);
+    return true;
+}
+
+} // namespace
+
+bool recon_check(const CodecMath &m, unsigned len, const uint32_t *lost, unsigned nlost) {
+    if (len < 1 || len > m.load || nlost > m.spec.nroots || (nlost && !lost)) return false;
+    const unsigned S = len + m.spec.nroots;
+    std::vector<uint8_t> seen(S, 0);
+    for (unsigned r = 0; r < nlost; ++r) {
+        if (lost[r] >= S || seen[lost[r]]) return false;
+        seen[lost[r]] = 1;
+    }
+    return true;
+}
+
+bool recon_build(const CodecMath &m, unsigned len, const uint32_t *lost, unsigned nlost,
+                 std::vector<uint16_t> &cols, std::vector<uint32_t> &surv) {
+    if (!recon_check(m, len, lost, nlost)) return false;
+    const Field &gf = m.gf;
+    const unsigned NR = m.spec.nroots, S = len + NR, mm = m.spec.mm, nsurv = S - nlost;
+    std::vector<uint8_t> gone(S, 0);
+    for (unsigned r = 0; r < nlost; ++r) gone[lost[r]] = 1;
+    surv.clear();
+    for (unsigned p = 0; p < S; ++p)
+        if (!gone[p]) surv.push_back(p);
+    std::vector<uint16_t> ainv((size_t)nlost * nlost), xl((size_t)NR * nlost);
+    for (unsigned i = 0; i < NR; ++i)
+        for (unsigned r = 0; r < nlost; ++r) xl[(size_t)i * nlost + r] = (uint16_t)recon_x(m, i, S, lost[r]);
+    std::copy(xl.begin(), xl.begin() + (size_t)nlost * nlost, ainv.begin());   // A[i][r]
+    if (nlost && !gf_invert(gf, ainv, nlost)) return false;                    // ainv[r][i]
+    // R, one survivor column at a time
+    cols.assign((size_t)NR * nsurv * mm, 0);
+    std::vector<uint16_t> xs(NR), R(NR);
+    for (unsigned c = 0; c < nsurv; ++c) {
+        for (unsigned i = 0; i < NR; ++i) xs[i] = (uint16_t)recon_x(m, i, S, surv[c]);
+        for (unsigned r = 0; r < nlost; ++r) {
+            unsigned v = 0;
+            for (unsigned i = 0; i < nlost; ++i) v ^= gf.mul(ainv[(size_t)r * nlost + i], xs[i]);
+            R[r] = (uint16_t)v;
+        }
+        for (unsigned i = nlost; i < NR; ++i) {
+            unsigned v = xs[i];
+            for (unsigned r = 0; r < nlost; ++r) v ^= gf.mul(xl[(size_t)i * nlost + r], R[r]);
+            R[i] = (uint16_t)v;
+        }
+        for (unsigned b = 0; b < mm; ++b) {
+            const unsigned e = m.spec.dual ? m.from_dual[1u << b] : 1u << b;
+            for (unsigned r = 0; r < NR; ++r) {
+                const unsigned v = gf.mul(R[r], e);
+                cols[((size_t)r * nsurv + c) * mm + b] = (uint16_t)(m.spec.dual ? m.into_dual[v] : v);
+            }
+        }
+    }
+    return true;
+}
+
+// Rows of the device table per (survivor, bit): NROOTS rounded up to the row block that serves it,
+// so that a row block's scalar loads never leave the table; rows past NROOTS are zero.
+unsigned recon_row_pad(unsigned nroots) {
+    for (unsigned rb = 4; rb < 32; rb *= 2)
+        if (nroots <= rb) return rb;
+    return (nroots + 31) / 32 * 32;
+}
+
+// Dwords of the coefficient part of the table.  m <= 8: per survivor, group of three symbol bits and
+// row, the 8 byte-wide images of the group's values (two dwords; apply8).  m > 8: per survivor, bit
+// and row, the bit's column replicated across the dword (apply).
+static size_t recon_coef_words(unsigned mm, unsigned nroots, unsigned nsurv) {
+    const size_t per = mm <= 8 ? (size_t)((mm + 2) / 3) * 2 : mm;
+    return (size_t)nsurv * per * recon_row_pad(nroots);
+}
+
+size_t recon_table_words(unsigned mm, unsigned nroots, unsigned nsurv, unsigned nlost) {
+    return recon_coef_words(mm, nroots, nsurv) + nsurv + nlost + recon_row_pad(nroots);
+}
+
+void recon_table(unsigned mm, unsigned nroots, const std::vector<uint16_t> &cols,
+                 const std::vector<uint32_t> &surv, const uint32_t *lost, unsigned nlost,
+                 std::vector<uint32_t> &tab) {
+    const unsigned nsurv = (unsigned)surv.size(), nrp = recon_row_pad(nroots);
+    tab.assign(recon_table_words(mm, nroots, nsurv, nlost), 0);
+    uint32_t *tail = tab.data() + recon_coef_words(mm, nroots, nsurv);
+    std::copy(surv.begin(), surv.end(), tail);
+    std::copy(lost, lost + nlost, tail + nsurv);
+    if (mm <= 8) {
+        const unsigned G = (mm + 2) / 3;
+        for (unsigned r = 0; r < nroots; ++r)
+            for (unsigned c = 0; c < nsurv; ++c)
+                for (unsigned g = 0; g < G; ++g) {
+                    uint32_t *e = &tab[(((size_t)c * G + g) * nrp + r) * 2];
+                    for (unsigned v = 1; v < 8; ++v) {          // image of the group value v
+                        uint32_t img = 0;
+                        for (unsigned i = 0; i < 3 && 3 * g + i < mm; ++i)
+                            if (v >> i & 1) img ^= cols[((size_t)r * nsurv + c) * mm + 3 * g + i];
+                        e[v >> 2] |= img << 8 * (v & 3);
+                    }
+                }
+        return;                                     // no constant to take out: `fix` stays zero
+    }
+    for (unsigned r = 0; r < nroots; ++r)
+        for (unsigned c = 0; c < nsurv; ++c)
+            for (unsigned b = 0; b < mm; ++b)
+                tab[((size_t)c * mm + b) * nrp + r] = cols[((size_t)r * nsurv + c) * mm + b] * 0x00010001u;
+    uint32_t *fix = tail + nsurv + nlost;           // see apply()
+    for (size_t i = 0; i < (size_t)nsurv * mm; ++i)
+        for (unsigned r = 0; r < nrp; ++r) fix[r] ^= tab[i * nrp + r] & 0x7fff7fffu;
+}
+
+namespace recon {
+
+constexpr unsigned kUnroll = 4;                   // survivors whose loads are in flight together
+
+// V dwords per lane (4: one dwordx4; 1: one dword) or V = 0: one element.
+template <typename T, int V>
+struct Run {
+    static constexpr int ND = V ? V : 1;
+    static constexpr unsigned EPL = V ? V * (4 / sizeof(T)) : 1;   // codewords per lane
+    static __device__ __forceinline__ void load(const T *p, uint32_t (&x)[ND]) {
+        if constexpr (V == 4) {
+            const uint4 v = *reinterpret_cast<const uint4 *>(p);
+            x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
+        } else if constexpr (V == 1) {
+            x[0] = *reinterpret_cast<const uint32_t *>(p);
+        } else {
+            x[0] = *p;
+        }
+    }
+    static __device__ __forceinline__ void store(T *p, const uint32_t (&x)[ND]) {
+        if constexpr (V == 4) *reinterpret_cast<uint4 *>(p) = make_uint4(x[0], x[1], x[2], x[3]);
+        else if constexpr (V == 1) *reinterpret_cast<uint32_t *>(p) = x[0];
+        else *p = (T)x[0];
+    }
+};
+
+// One survivor's dwords x into the accumulators of a row block; kp: its columns, bit b at
+// kp + b * nrp.  MB: the symbol bits when known at compile time (the bit loop is then unrolled and
+// the columns' scalar loads are issued ahead), else 0 and mm is used.
+// bit + 0x7f.. is 0x80.. in the codewords whose bit is set and 0x7f.. in the others, i.e. the mask
+// 0xff.. / 0x00.. XOR the constant 0x7f..: one add instead of a shift and a subtract (which the
+// compiler turns into a quarter-rate multiply by 0xff).  What the constant adds to an accumulator,
+// XOR over all survivors and bits of K & 0x7f.., does not depend on the data: the table carries it
+// per row (`fix`) and the kernel takes it out once at the end.
+template <int RB, int ND, int MB>
+__device__ __forceinline__ void apply(const uint32_t (&x)[ND], const uint32_t *__restrict__ kp, unsigned nrp,
+                                      unsigned mm, uint32_t ones, uint32_t low, uint32_t (&acc)[RB][ND]) {
+    auto bit = [&](unsigned b, const uint32_t *__restrict__ kb) {
+        uint32_t d[ND];
+#pragma unroll
+        for (int i = 0; i < ND; ++i) d[i] = ((x[i] >> b) & ones) + low;
+#pragma unroll
+        for (int r = 0; r < RB; ++r) {
+            const uint32_t k = kb[r];
+#pragma unroll
+            for (int i = 0; i < ND; ++i)            // acc ^= d & k as one v_bitop3
+                acc[r][i] = __builtin_amdgcn_bitop3_b32(acc[r][i], d[i], k, 0x78);
+        }
+    };
+    if constexpr (MB != 0) {
+#pragma unroll
+        for (unsigned b = 0; b < MB; ++b) bit(b, kp + (size_t)b * nrp);
+    } else {
+        for (unsigned b = 0; b < mm; ++b, kp += nrp) bit(b, kp);
+    }
+}
+
+// The byte form (m <= 8): a GF(2)-linear map of a byte is the XOR of its images on groups of three
+// bits, and v_perm_b32 is an 8-entry byte table lookup for the four codewords of a dword at once:
+// selector = the group's value in each byte, table = the 8 images of a row (two dwords, kp[2 r] and
+// kp[2 r + 1]; group g at kp + g * 2 * nrp).  Three lookups and two XORs (one of them a three-input
+// v_bitop3) per row and dword for m = 8, against eight v_bitop3 in the bit-column form, and five
+// shared instructions per dword instead of 24.  MB == 8: the three groups unrolled; else a loop
+// over the groups of mm bits, bits at and above mm masked out of the selectors.
+template <int RB, int ND, int MB>
+__device__ __forceinline__ void apply8(const uint32_t (&x)[ND], const uint32_t *__restrict__ kp, unsigned nrp,
+                                       unsigned mm, uint32_t (&acc)[RB][ND]) {
+    if constexpr (MB == 8) {
+        uint32_t i0[ND], i1[ND], i2[ND];
+#pragma unroll
+        for (int i = 0; i < ND; ++i) {
+            i0[i] = x[i] & 0x07070707u;
+            i1[i] = (x[i] >> 3) & 0x07070707u;
+            i2[i] = (x[i] >> 6) & 0x03030303u;
+        }
+#pragma unroll
+        for (int r = 0; r < RB; ++r) {
+            const uint32_t a0 = kp[2 * r], a1 = kp[2 * r + 1];
+            const uint32_t b0 = kp[2 * nrp + 2 * r], b1 = kp[2 * nrp + 2 * r + 1];
+            const uint32_t c0 = kp[4 * nrp + 2 * r];
+#pragma unroll
+            for (int i = 0; i < ND; ++i) {
+                const uint32_t p0 = __builtin_amdgcn_perm(a1, a0, i0[i]);
+                const uint32_t p1 = __builtin_amdgcn_perm(b1, b0, i1[i]);
+                const uint32_t p2 = __builtin_amdgcn_perm(c0, c0, i2[i]);
+                acc[r][i] = __builtin_amdgcn_bitop3_b32(acc[r][i], p0, p1, 0x96) ^ p2;   // three-input XOR
+            }
+        }
+    } else {
+        for (unsigned g = 0; 3 * g < mm; ++g, kp += 2 * nrp) {
+            const unsigned nb = mm - 3 * g < 3 ? mm - 3 * g : 3;
+            const uint32_t msk = ((1u << nb) - 1u) * 0x01010101u;
+            uint32_t idx[ND];
+#pragma unroll
+            for (int i = 0; i < ND; ++i) idx[i] = (x[i] >> 3 * g) & msk;
+#pragma unroll
+            for (int r = 0; r < RB; ++r) {
+                const uint32_t t0 = kp[2 * r], t1 = kp[2 * r + 1];
+#pragma unroll
+                for (int i = 0; i < ND; ++i) acc[r][i] ^= __builtin_amdgcn_perm(t1, t0, idx[i]);
+            }
+        }
+    }
+}
+
+// Two survivors of m = 8 symbols at once: their six lookups go into an accumulator with three
+// three-input XORs (two and a half instructions less per row and dword than one by one).
+template <int RB, int ND>
+__device__ __forceinline__ void apply8x2(const uint32_t (&x)[ND], const uint32_t (&y)[ND],
+                                         const uint32_t *__restrict__ kx, const uint32_t *__restrict__ ky,
+                                         unsigned nrp, uint32_t (&acc)[RB][ND]) {
+    uint32_t ix[3][ND], iy[3][ND];
+#pragma unroll
+    for (int i = 0; i < ND; ++i) {
+        ix[0][i] = x[i] & 0x07070707u;
+        ix[1][i] = (x[i] >> 3) & 0x07070707u;
+        ix[2][i] = (x[i] >> 6) & 0x03030303u;
+        iy[0][i] = y[i] & 0x07070707u;
+        iy[1][i] = (y[i] >> 3) & 0x07070707u;
+        iy[2][i] = (y[i] >> 6) & 0x03030303u;
+    }
+#pragma unroll
+    for (int r = 0; r < RB; ++r) {
+        const uint32_t a0 = kx[2 * r], a1 = kx[2 * r + 1], b0 = kx[2 * nrp + 2 * r], b1 = kx[2 * nrp + 2 * r + 1],
+                       c0 = kx[4 * nrp + 2 * r];
+        const uint32_t d0 = ky[2 * r], d1 = ky[2 * r + 1], e0 = ky[2 * nrp + 2 * r], e1 = ky[2 * nrp + 2 * r + 1],
+                       f0 = ky[4 * nrp + 2 * r];
+#pragma unroll
+        for (int i = 0; i < ND; ++i) {
+            uint32_t v = acc[r][i];
+            v = __builtin_amdgcn_bitop3_b32(v, __builtin_amdgcn_perm(a1, a0, ix[0][i]),
+                                            __builtin_amdgcn_perm(b1, b0, ix[1][i]), 0x96);
+            v = __builtin_amdgcn_bitop3_b32(v, __builtin_amdgcn_perm(c0, c0, ix[2][i]),
+                                            __builtin_amdgcn_perm(d1, d0, iy[0][i]), 0x96);
+            acc[r][i] = __builtin_amdgcn_bitop3_b32(v, __builtin_amdgcn_perm(e1, e0, iy[1][i]),
+                                                    __builtin_amdgcn_perm(f0, f0, iy[2][i]), 0x96);
+        }
+    }
+}
+
+// All survivors of the lane's run into the accumulators of the row block that starts at row r0:
+// kUnroll survivors' loads are issued together, the ragged end goes one by one.
+template <typename T, int RB, int V, int MB>
+__device__ __forceinline__ void sweep(const ReconArgs &a, const T *base, const uint32_t *__restrict__ K,
+                                      unsigned r0, const uint32_t *__restrict__ surv,
+                                      uint32_t (&acc)[RB][Run<T, V>::ND]) {
+    using R = Run<T, V>;
+    constexpr int ND = R::ND;
+    constexpr bool BYTES = sizeof(T) == 1;
+    const unsigned mm = MB ? MB : a.mm;
+    const size_t kstep = BYTES ? (size_t)((mm + 2) / 3) * 2 * a.nrp : (size_t)mm * a.nrp;
+    K += BYTES ? 2 * r0 : r0;
+    auto one = [&](const uint32_t (&x)[ND], unsigned c) {
+        if constexpr (BYTES) apply8<RB, ND, MB>(x, K + c * kstep, a.nrp, mm, acc);
+        else apply<RB, ND, MB>(x, K + c * kstep, a.nrp, mm, 0x00010001u, 0x7fff7fffu, acc);
+    };
+    unsigned c = 0;
+    for (; c + kUnroll <= a.nsurv; c += kUnroll) {
+        uint32_t x[kUnroll][ND];
+#pragma unroll
+        for (unsigned u = 0; u < kUnroll; ++u) R::load(base + (size_t)surv[c + u] * a.sym_stride, x[u]);
+        if constexpr (BYTES && MB == 8) {
+#pragma unroll
+            for (unsigned u = 0; u < kUnroll; u += 2)
+                apply8x2<RB, ND>(x[u], x[u + 1], K + (c + u) * kstep, K + (c + u + 1) * kstep, a.nrp, acc);
+        } else {
+#pragma unroll
+            for (unsigned u = 0; u < kUnroll; ++u) one(x[u], c + u);
+        }
+    }
+    for (; c < a.nsurv; ++c) {
+        uint32_t x[ND];
+        R::load(base + (size_t)surv[c] * a.sym_stride, x);
+        one(x, c);
+    }
+}
+
+// K: the coefficients; surv / lost: the positions; fix: [nrp] (recon_table).
+template <typename T, int RB, int V>
+__global__ void __launch_bounds__(256) k_recon(ReconArgs a, const uint32_t *__restrict__ K,
+                                               const uint32_t *__restrict__ surv,
+                                               const uint32_t *__restrict__ lost,
+                                               const uint32_t *__restrict__ fix) {
+    using R = Run<T, V>;
+    constexpr int ND = R::ND;
+    constexpr unsigned W = 8 * sizeof(T);
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= a.runs * a.nf) return;
+    size_t f, q;
+    if (((t | a.runs) >> 32) == 0) {                // 32-bit division (see shard_row)
+        const uint32_t t32 = (uint32_t)t, r32 = (uint32_t)a.runs, f32 = t32 / r32;
+        f = f32;
+        q = t32 - f32 * r32;
+    } else {
+        f = t / a.runs;
+        q = t - f * a.runs;
+    }
+    const size_t j = a.j0 + q * R::EPL;
+    T *const base = static_cast<T *>(a.frames) + (a.f0 + f) * a.frame_pitch + j;
+    uint32_t bad[ND];
+#pragma unroll
+    for (int d = 0; d < ND; ++d) bad[d] = 0;
+    for (unsigned r0 = 0; r0 < a.nrows; r0 += RB) {
+        uint32_t acc[RB][ND];
+#pragma unroll
+        for (int r = 0; r < RB; ++r)
+#pragma unroll
+            for (int d = 0; d < ND; ++d) acc[r][d] = 0;
+        if (a.mm == 8) sweep<T, RB, V, 8>(a, base, K, r0, surv, acc);
+        else sweep<T, RB, V, 0>(a, base, K, r0, surv, acc);
+#pragma unroll
+        for (int r = 0; r < RB; ++r) {
+            const unsigned row = r0 + r;
+            const uint32_t fx = fix[row];
+#pragma unroll
+            for (int d = 0; d < ND; ++d) acc[r][d] ^= fx;
+            if (row < a.nlost) {
+                R::store(base + (size_t)lost[row] * a.sym_stride, acc[r]);
+            } else {                                // check rows; the padding rows are zero
+#pragma unroll
+                for (int d = 0; d < ND; ++d) bad[d] |= acc[r][d];
+            }
+        }
+    }
+    if (a.result) {
+        int32_t *res = a.result + (a.f0 + f) * a.depth + j;
+        constexpr unsigned EPD = V ? 4 / sizeof(T) : 1;
+#pragma unroll
+        for (int d = 0; d < ND; ++d)
+#pragma unroll
+            for (unsigned e = 0; e < EPD; ++e) {
+                const uint32_t v = V ? (bad[d] >> (W * e)) & ((1u << W) - 1u) : bad[d];
+                res[d * EPD + e] = v ? -1 : (int32_t)a.nlost;
+            }
+    }
+}
+
+template <typename T, int V>
+static void launch_rb(unsigned rb, dim3 grid, hipStream_t s, const ReconArgs &a, const uint32_t *K,
+                      const uint32_t *surv, const uint32_t *lost, const uint32_t *fix) {
+    const dim3 block(256);
+    switch (rb) {
+    case 4: hipLaunchKernelGGL((k_recon<T, 4, V>), grid, block, 0, s, a, K, surv, lost, fix); break;
+    case 8: hipLaunchKernelGGL((k_recon<T, 8, V>), grid, block, 0, s, a, K, surv, lost, fix); break;
+    case 16: hipLaunchKernelGGL((k_recon<T, 16, V>), grid, block, 0, s, a, K, surv, lost, fix); break;
+    default:                                        // 32 rows: the bit-column form only (launch())
+        if constexpr (sizeof(T) == 2) hipLaunchKernelGGL((k_recon<T, 32, V>), grid, block, 0, s, a, K, surv, lost, fix);
+        break;
+    }
+}
+
+// Codewords [j0, j0 + n) of every frame, `epl` per lane.
+template <typename T, int V>
+static hipError_t launch_span(ReconArgs a, unsigned rb, size_t j0, size_t n, size_t nframes,
+                              const uint32_t *tab, hipStream_t s) {
+    constexpr size_t EPL = Run<T, V>::EPL;
+    if (!n) return hipSuccess;
+    a.j0 = j0;
+    a.runs = n / EPL;
+    const size_t per = a.mm <= 8 ? (size_t)((a.mm + 2) / 3) * 2 : a.mm;   // recon_coef_words
+    const uint32_t *K = tab, *surv = tab + (size_t)a.nsurv * per * a.nrp, *lost = surv + a.nsurv,
+                   *fix = lost + a.nlost;
+    const size_t maxt = (size_t)1 << 38;            // threads per launch (2^30 workgroups)
+    if (a.runs > maxt) return hipErrorInvalidValue;
+    const size_t fstep = maxt / a.runs;
+    for (size_t f0 = 0; f0 < nframes; f0 += fstep) {
+        a.f0 = f0;
+        a.nf = nframes - f0 < fstep ? nframes - f0 : fstep;
+        const dim3 grid((unsigned)((a.runs * a.nf + 255) / 256));
+        launch_rb<T, V>(rb, grid, s, a, K, surv, lost, fix);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+template <typename T>
+static hipError_t launch(ReconArgs a, size_t nframes, const uint32_t *tab, hipStream_t s) {
+    // rows per block: the byte form stops at 16 (at 32 its 192 table dwords per survivor no longer
+    // fit the scalar registers and the kernel ran 1.5 x slower than two passes of 16)
+    const unsigned cap = sizeof(T) == 1 ? 16 : 32;
+    unsigned rb = 4;
+    while (rb < cap && rb < a.nrows) rb *= 2;
+    // widest access every symbol row of every frame is aligned for
+    const size_t w = sizeof(T);
+    size_t al = (size_t)(uintptr_t)a.frames | a.sym_stride * w;
+    if (nframes > 1) al |= a.frame_pitch * w;
+    const size_t e16 = 16 / w, e4 = 4 / w;
+    size_t done = 0;
+    hipError_t e = hipSuccess;
+    if ((al & 15) == 0 && a.depth >= e16) {
+        done = a.depth / e16 * e16;
+        e = launch_span<T, 4>(a, rb, 0, done, nframes, tab, s);
+    } else if ((al & 3) == 0 && a.depth >= e4) {
+        done = a.depth / e4 * e4;
+        e = launch_span<T, 1>(a, rb, 0, done, nframes, tab, s);
+    }
+    if (e == hipSuccess) e = launch_span<T, 0>(a, rb, done, a.depth - done, nframes, tab, s);   // ragged end
+    return e;
+}
+
+} // namespace recon
+
+hipError_t launch_recon(const ReconArgs &a, size_t nframes, const uint32_t *tab, hipStream_t s) {
+    if (!a.nrows || !nframes) return hipSuccess;
+    return a.mm <= 8 ? recon::launch<uint8_t>(a, nframes, tab, s) : recon::launch<uint16_t>(a, nframes, tab, s);
+}
+
+} // namespace ezrs
+
+extern "C" int ezrs_recon_bitmatrix(unsigned symbol_bits, unsigned poly, unsigned fcr, unsigned prim,
+                                    unsigned nroots, int dual, unsigned len, const uint32_t *lost,
+                                    unsigned nlost, uint16_t *cols, size_t cols_cap, uint32_t *survivors) {
+    using namespace ezrs;
+    if (!cols || !survivors) return -EINVAL;
+    CodecMath m;
+    if (!m.build(CodecSpec{symbol_bits, poly, fcr, prim, nroots, dual ? 1 : 0})) return -EINVAL;
+    if (!recon_check(m, len, lost, nlost)) return -EINVAL;
+    const size_t nsurv = (size_t)len + nroots - nlost;
+    if (cols_cap < (size_t)nroots * nsurv * symbol_bits) return -EINVAL;
+    try {
+        std::vector<uint16_t> c;
+        std::vector<uint32_t> sv;
+        if (!recon_build(m, len, lost, nlost, c, sv)) return -EINVAL;
+        std::copy(c.begin(), c.end(), cols);
+        std::copy(sv.begin(), sv.end(), survivors);
+    } catch (const std::bad_alloc &) {
+        return -ENOMEM;
+    }
+    return 0;
+}

@@ -100,6 +100,10 @@ def lib():
                                               _vp, _sz, _vp, _sz, _vp]
         L.ezrs_decode_interleaved_ws.argtypes = [_vp, _vp, _sz, _sz, _sz, _u, _sz, _vp, _sz, _vp,
                                                  _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp]
+        L.ezrs_recon_create.argtypes = [C.POINTER(_vp), _vp, _u, _vp, _u]
+        L.ezrs_recon_destroy.argtypes = [_vp]
+        L.ezrs_reconstruct_interleaved.argtypes = [_vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp]
+        L.ezrs_recon_bitmatrix.argtypes = [_u, _u, _u, _u, _u, _i, _u, _vp, _u, _vp, _sz, _vp]
         L.ezrs_kernel_path.argtypes = [_vp]
         L.ezrs_set_launch_rows.argtypes = [_vp, _sz]
         L.ezrs_set_semantics.argtypes = [_vp, _i]
@@ -388,6 +392,12 @@ class Codec:
             "ezrs_decode_interleaved")
         return result
 
+    def recon_plan(self, length, lost):
+        """Reconstruction plan for codewords of `length` data symbols whose symbols at the
+        positions `lost` (relative to the first data symbol, parity at length..) are gone in
+        every codeword -- ezrs_recon_create.  Returns a Recon."""
+        return Recon(self, length, lost)
+
     # -- host batch forms ----------------------------------------------------------------------
     def encode_host(self, data, length=None, parity=None, chunk=0):
         """data: [ncw, stride] numpy rows (only read); parity: [ncw, >=nroots] array, or None:
@@ -447,6 +457,83 @@ class Codec:
         if rc not in (0, -errno.EMSGSIZE):
             _check(rc, "ezrs_stream_decode")
         return out[:n.value].tobytes(), nf.value, rc == 0
+
+
+class Recon:
+    """A reconstruction plan (ezrs_recon_create): one loss pattern shared by every codeword, solved
+    once; ``reconstruct`` rebuilds the lost symbols of interleaved frames in place.  The plan keeps
+    nothing of the codec it was made from.
+
+    * ``lost``       the lost positions, in the order given (the order of the rebuild rows)
+    * ``survivors``  the surviving positions, ascending
+    * ``nlost``      len(lost); ``result`` entries are nlost or -1"""
+
+    def __init__(self, codec, length, lost):
+        self.lost = [int(p) for p in lost]
+        self.nlost = len(self.lost)
+        self.length, self.nroots, self.device = int(length), codec.nroots, codec.device
+        self._w = codec.info.datum_bytes
+        arr = (C.c_uint32 * max(self.nlost, 1))(*self.lost)
+        h = _vp()
+        self._h = None
+        _check(lib().ezrs_recon_create(C.byref(h), codec._h, self.length, arr, self.nlost),
+               "ezrs_recon_create")
+        self._h = h
+        gone = set(self.lost)
+        self.survivors = [p for p in range(self.length + self.nroots) if p not in gone]
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            try:
+                lib().ezrs_recon_destroy(h)
+            except Exception:
+                pass
+            self._h = None
+
+    def reconstruct(self, frames, result=None, stream=None):
+        """frames: [nframes, length + nroots, depth] device tensor as in Codec.encode_interleaved;
+        the lost symbols of every codeword are overwritten, nothing else.  result: an int32 device
+        tensor [nframes * depth] (frame-major) that receives nlost, or -1 where the survivors are
+        not consistent with any codeword; None: no check.  Returns result."""
+        if not getattr(frames, "is_cuda", False):
+            raise EzrsError("frames: expected a GPU tensor")
+        if frames.device.index != self.device:
+            raise EzrsError(f"frames: tensor on cuda:{frames.device.index}, plan on cuda:{self.device}")
+        if frames.element_size() != self._w:
+            raise EzrsError(f"frames: expected {self._w}-byte elements, got {frames.dtype}")
+        if frames.dim() != 3 or (frames.shape[2] > 1 and frames.stride(2) != 1):
+            raise EzrsError("frames: expected a 3-D tensor [nframes, len + nroots, depth] with a "
+                            "contiguous last dimension")
+        nframes, nsym, depth = frames.shape
+        if nsym != self.length + self.nroots or depth == 0:
+            raise EzrsError(f"frames: {nsym} symbols per codeword, the plan has "
+                            f"{self.length + self.nroots}, and a depth of at least 1")
+        if result is not None:
+            _dev_rows(result, "result", self.device, 4, ndim=1)
+            if result.shape[0] < nframes * depth:
+                raise EzrsError("result: fewer entries than codewords")
+        _check(lib().ezrs_reconstruct_interleaved(
+            self._h, _tp(frames), frames.stride(0), frames.stride(1), depth, nframes, _tp(result),
+            _stream_ptr(stream)), "ezrs_reconstruct_interleaved")
+        return result
+
+
+def recon_bitmatrix(params, length, lost):
+    """The matrix of a reconstruction plan on the host (ezrs_recon_bitmatrix; no device).  params:
+    (symbol_bits, poly, fcr, prim, nroots, dual).  Returns (cols, survivors): cols a uint16 array
+    [nroots, nsurv, symbol_bits] -- rows 0..len(lost)-1 rebuild `lost` in the order given, the others
+    are check rows -- and the surviving positions, ascending."""
+    mm, poly, fcr, prim, nroots, dual = params
+    lost = [int(p) for p in lost]
+    nsurv = max(length + nroots - len(lost), 0)
+    cols = np.zeros((nroots, nsurv, mm), np.uint16)
+    surv = np.zeros(max(nsurv, 1), np.uint32)
+    arr = (C.c_uint32 * max(len(lost), 1))(*lost)
+    _check(lib().ezrs_recon_bitmatrix(mm, poly, fcr, prim, nroots, int(bool(dual)), length, arr,
+                                      len(lost), _np(cols), cols.size, _np(surv)),
+           "ezrs_recon_bitmatrix")
+    return cols, surv[:nsurv]
 
 
 class BCH:

@@ -227,6 +227,54 @@ int ezrs_decode_interleaved_ws(const ezrs_codec *codec, void *frames, size_t fra
                                int32_t *result, uint32_t *positions, size_t pos_stride, void *corr,
                                size_t corr_stride, void *ws, size_t ws_bytes, void *stream);
 
+/* Shared-erasure reconstruction of interleaved frames (device-resident).  Striped shards lose whole
+ * shards: every codeword of the stripe has the same erasure positions and no other errors.  A plan
+ * solves that erasure system once on the host; ezrs_reconstruct_interleaved then applies one
+ * constant GF(2^m) matrix to the surviving symbols, in place in the frames, with no staging and no
+ * workspace (the reference has no such call: it replaces decode() with the same eras_pos for every
+ * codeword, rs_base:1170-1242).
+ *   plan     `lost`: nlost (0..NROOTS) distinct HOST positions in 0..len+NROOTS-1, relative to the
+ *            codeword's first data symbol (parity follows at len..), in that frame under both
+ *            semantics of the codec.  ezrs_recon_create builds the matrix, uploads it to the
+ *            codec's device and may synchronise; the plan copies what it needs, so it stays valid
+ *            after ezrs_destroy(codec); it is const afterwards and may be shared by threads and
+ *            streams.  -EINVAL: null out or codec, len outside 1..load, nlost > NROOTS, a position
+ *            >= len + NROOTS or given twice; -ENOTSUP when the plan's device table would exceed
+ *            64 MiB (engine limit): for symbols wider than 8 bits it takes 4 bytes x symbol_bits x
+ *            survivors x NROOTS (rounded up to 4, 8, 16 or a multiple of 32), so full-length
+ *            RS(65535,65503) is such a case; no codec of up to 8 bits comes near it.
+ *   call     geometry as in ezrs_*_interleaved above; every frame of the call shares the plan's
+ *            loss pattern.  Asynchronous; never allocates, never synchronises.  For every codeword
+ *            k = f*depth + j the nlost lost symbols are overwritten with the values the first nlost
+ *            syndrome equations determine from the survivors, in the order of `lost`; their old
+ *            contents are never read.  No other element of `frames` is written.  Bits above the
+ *            symbol are ignored in survivors and zero in rebuilt symbols.
+ *   result   (nullable) int32[nframes*depth]: nlost if the remaining NROOTS - nlost syndromes of
+ *            the rebuilt word are zero, i.e. some codeword agrees with every survivor, else -1 (the
+ *            lost symbols are written all the same; fall back to ezrs_decode_interleaved for that
+ *            stripe).  Up to NROOTS - nlost wrong survivor symbols always give -1; with nlost ==
+ *            NROOTS nothing can be checked and the result is nlost.  With result == NULL the check
+ *            is not computed.  nlost == 0 writes nothing to `frames`: a verify (0 or -1).
+ * -EINVAL: null plan or frames; depth == 0; sym_stride < depth; nframes > 1 with frame_pitch <
+ * (len + NROOTS - 1)*sym_stride + depth.  nframes == 0 returns 0 and touches nothing. */
+typedef struct ezrs_recon ezrs_recon;
+int ezrs_recon_create(ezrs_recon **out, const ezrs_codec *codec, unsigned len, const uint32_t *lost,
+                      unsigned nlost);
+int ezrs_recon_destroy(ezrs_recon *plan);   /* NULL: 0 */
+int ezrs_reconstruct_interleaved(const ezrs_recon *plan, void *frames, size_t frame_pitch,
+                                 size_t sym_stride, size_t depth, size_t nframes, int32_t *result,
+                                 void *stream);
+/* The plan's matrix on the host, from the codec parameters of ezrs_create (no device is touched).
+ * cols: NROOTS * nsurv * symbol_bits uint16 (cols_cap: entries available), [row][survivor][bit]:
+ * the image, in the stored representation (dual basis where the codec has it), of bit `bit` of
+ * survivor `survivor` in output row `row`; an output symbol is the XOR of the entries of the set
+ * bits of all survivors.  Rows 0..nlost-1 rebuild lost[0..nlost-1] in the order given, the others
+ * are the check rows.  survivors: the nsurv = len + NROOTS - nlost surviving positions, ascending.
+ * -EINVAL: invalid codec parameters, the plan rules above, null outputs, cols_cap too small. */
+int ezrs_recon_bitmatrix(unsigned symbol_bits, unsigned poly, unsigned fcr, unsigned prim,
+                         unsigned nroots, int dual, unsigned len, const uint32_t *lost,
+                         unsigned nlost, uint16_t *cols, size_t cols_cap, uint32_t *survivors);
+
 /* Host-memory forms: the same contracts with HOST pointers.  The batch is streamed through the
  * device in chunks of `chunk` codewords (0 = library default) over two HIP streams with
  * asynchronous copies; pinned host memory (ezrs_host_alloc) gets full PCIe overlap.  Blocking:
