@@ -14,18 +14,23 @@
 // for RS(255,223).  Encode evaluates the syndromes of the data positions; k_ps_parity8 maps them to
 // parity (parity = V^-1 S, bit-sliced over 32 codewords per lane).
 //
-// Tile kernel k_pt_lin: one 512-thread workgroup (8 waves) per 256-codeword tile, two workgroups per
-// CU (80 KiB of LDS each, <= 128 VGPRs: 4 waves per SIMD), persistent over tiles.
+// Tile kernels: one workgroup per 256-codeword tile, two workgroups per CU (80 KiB of LDS each),
+// persistent over tiles.  Two kernels, one per codec (launch_tile), on one skeleton (tile_run,
+// wave_tail):
+//   k_pq_lin  4 waves (<= 256 VGPRs, 2 waves per SIMD): every wave evaluates every leader over its
+//             own run of positions.  RS(255,223) and the other codecs of codegen's PQ_CODECS.
+//   k_pt_lin  8 waves (<= 128 VGPRs, 4 waves per SIMD): leader groups x position quarters.  The
+//             remaining codecs (NR 1, 2, 3, 7, 9).
+// They differ in the main loop alone (pq::Tile::pass, pt::Tile::pass).  The skeleton:
 //   * The tile's rows are one contiguous span of HBM; 1 KiB LDS-DMA instructions copy it to LDS as it
 //     lies (every line fetched once), the next tile's while this tile's epilogue runs.  Lane l owns
 //     rows 4l .. 4l+3 (byte k of its words = row 4l + k); with an odd pitch the row starts fall in 32
 //     distinct banks, so the row reads (4-byte aligned, then v_alignbyte) are conflict-free.
-//   * Waves split the leaders into GN groups and the 16-position pieces into QN = 8 / GN quarters;
-//     every quarter runs quarter 0's networks and then multiplies its partials by alpha^(-16 q e).
 //   * A recursive-halving exchange through the consumed image leaves every wave the totals of the
-//     leaders its generated epilogue folds: 4 syndromes (one quad) per wave.
-//   * Shard batches (SH): per-row offsets and pads come from a per-tile row table; the bytes before a
-//     shortened row's own pad (the previous row's, in the linear image) are masked off.
+//     leaders its generated epilogue folds: NQ quads of 4 syndromes per wave.
+//   * Shard batches (SH): per-row offsets and pads come from a per-tile row table, each wave writing
+//     256 / waves of its rows; the bytes before a shortened row's own pad (the previous row's, in
+//     the linear image) are masked off.
 //   * All LDS traffic, LDS-DMA and global stores are inline asm with counted s_waitcnt: the
 //     compiler would otherwise wait for every DMA in flight at each LDS access or barrier.
 //   * Measured and dropped: a row-pitched, swizzled image gathered by unaligned per-lane LDS-DMA
@@ -36,6 +41,7 @@
 //     next chunk's workspace loads in flight during the map): 0.149 vs 0.144 ms.
 //
 #include "ezrs_internal.hpp"
+#include "ezrs_tile_prims.hpp"
 
 #include <atomic>
 #include "gen/ezrs_ps_tables.inc"
@@ -49,31 +55,30 @@
 namespace ezrs {
 namespace ps {
 
+using namespace tile;                               // lane_id, make_rsrc, lds_addr, transpose4x4, gather4, Raw ...
+
 constexpr int kTile = 256;                          // codewords per tile
 constexpr int32_t kSentinel = INT32_MIN;
 constexpr int kN = 255;
 
-typedef __attribute__((address_space(3))) void lds_void;
-
 #ifdef EZRS_PS_STAMPS
-// tools/micro/pt_stamps.hip: phase stamps of the linear tile kernel, [wg][wave][tile][phase]
-__device__ unsigned long long g_pt_stamps[16][8][8][8];
-#define PT_STAMP(ph) do { __builtin_amdgcn_sched_barrier(0); if (blockIdx.x < 16 && pt_it < 8 && \
-    __lane_id() == 0) g_pt_stamps[blockIdx.x][pt_w][pt_it][ph] = __builtin_amdgcn_s_memtime(); \
-    __builtin_amdgcn_sched_barrier(0); } while (0)
-// tools/micro/pq_stamps.hip: the same for the 4-wave kernel, [wg][wave][tile][phase]
+// tools/micro/pq_stamps.hip: phase stamps of the tile skeleton (tile_run / wave_tail, which name
+// K, W and it), [wg][wave][tile][phase].  The arrays hold the 4-wave kernel's waves, so the 8-wave
+// kernel is not stamped.
 __device__ unsigned long long g_pq_stamps[512][4][9][8];
 __device__ unsigned long long g_pq_rt[512][4];             // wave 0: realtime + memtime at start / end
 __device__ unsigned g_pq_hw[512][2];                       // wave 0: HW_ID, XCC_ID
-#define PQ_STAMP(ph) do { __builtin_amdgcn_sched_barrier(0); if (blockIdx.x < 512 && pq_it < 9 && \
-    __lane_id() == 0) g_pq_stamps[blockIdx.x][W][pq_it][ph] = __builtin_amdgcn_s_memtime(); \
-    __builtin_amdgcn_sched_barrier(0); } while (0)
-#define PQ_RT(i) do { __builtin_amdgcn_sched_barrier(0); if (blockIdx.x < 512 && W == 0 && __lane_id() == 0) { \
-    g_pq_rt[blockIdx.x][2 * (i)] = __builtin_amdgcn_s_memrealtime(); \
-    g_pq_rt[blockIdx.x][2 * (i) + 1] = __builtin_amdgcn_s_memtime(); \
-    if ((i) == 0) { g_pq_hw[blockIdx.x][0] = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11)); \
-                    g_pq_hw[blockIdx.x][1] = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (31 << 11)); } } \
-    __builtin_amdgcn_sched_barrier(0); } while (0)
+#define TILE_STAMP(ph) do { if constexpr (K::kWaves == 4) { __builtin_amdgcn_sched_barrier(0); \
+    if (blockIdx.x < 512 && it < 9 && __lane_id() == 0) \
+        g_pq_stamps[blockIdx.x][W][it][ph] = __builtin_amdgcn_s_memtime(); \
+    __builtin_amdgcn_sched_barrier(0); } } while (0)
+#define TILE_RT(i) do { if constexpr (K::kWaves == 4) { __builtin_amdgcn_sched_barrier(0); \
+    if (blockIdx.x < 512 && W == 0 && __lane_id() == 0) { \
+        g_pq_rt[blockIdx.x][2 * (i)] = __builtin_amdgcn_s_memrealtime(); \
+        g_pq_rt[blockIdx.x][2 * (i) + 1] = __builtin_amdgcn_s_memtime(); \
+        if ((i) == 0) { g_pq_hw[blockIdx.x][0] = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11)); \
+                        g_pq_hw[blockIdx.x][1] = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (31 << 11)); } } \
+    __builtin_amdgcn_sched_barrier(0); } } while (0)
 // tools/micro/par_stamps.hip: the parity kernel's phases, [block][wave][phase]
 __device__ unsigned long long g_par_stamps[64][8][8];
 __device__ unsigned long long g_par_rt[4096][2];           // s_memrealtime (100 MHz) at wave 0's start / end
@@ -85,9 +90,8 @@ __device__ unsigned g_par_hw[4096];                        // HW_ID of wave 0
         if (ph == 0) g_par_hw[blockIdx.x] = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11)); } } \
     __builtin_amdgcn_sched_barrier(0); } while (0)
 #else
-#define PT_STAMP(ph) do { } while (0)
-#define PQ_STAMP(ph) do { } while (0)
-#define PQ_RT(i) do { } while (0)
+#define TILE_STAMP(ph) do { } while (0)
+#define TILE_RT(i) do { } while (0)
 #define PAR_STAMP(ph) do { } while (0)
 #endif
 
@@ -105,8 +109,6 @@ struct PsArgs {
     uint32_t srows;             // shard batches (Shards): codewords per shard, 0 = a plain batch
     int stail_lo;               // full-frame position of a shard's last row's first byte
     uint32_t spitch;            // shard pitch in bytes
-    int ablate;                 // timing experiments only (tools/pt_ablate.py, EZRS_PT_ABLATE): bit 0
-                                // no main loop, 1 no exchange, 2 no fold, 3 no DMA, 5 nothing flagged
     uint32_t *flag;             // decode: gen stored here when a codeword is flagged (DecodeArgs)
     uint32_t gen;
 };
@@ -134,64 +136,18 @@ __device__ __forceinline__ void transpose8(uint32_t (&D)[8]) {
     }
 }
 
-// 4x4 byte transpose: out[t] byte k = in[k] byte t.
-__device__ __forceinline__ void transpose4x4(const uint32_t (&a)[4], uint32_t *out) {
-    const uint32_t t01 = __builtin_amdgcn_perm(a[1], a[0], 0x05010400u);
-    const uint32_t t23 = __builtin_amdgcn_perm(a[3], a[2], 0x05010400u);
-    const uint32_t u01 = __builtin_amdgcn_perm(a[1], a[0], 0x07030602u);
-    const uint32_t u23 = __builtin_amdgcn_perm(a[3], a[2], 0x07030602u);
-    out[0] = __builtin_amdgcn_perm(t23, t01, 0x05040100u);
-    out[1] = __builtin_amdgcn_perm(t23, t01, 0x07060302u);
-    out[2] = __builtin_amdgcn_perm(u23, u01, 0x05040100u);
-    out[3] = __builtin_amdgcn_perm(u23, u01, 0x07060302u);
-}
-
-// ---- LDS and buffer-resource helpers ----------------------------------------------------------
-__device__ __forceinline__ uint32_t lds_addr(const uint8_t *p) {
-    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint8_t *)p;
-}
-
-typedef int pw_rsrc_t __attribute__((ext_vector_type(4)));
-
-// Buffer descriptor of [base, base + span): raw (stride 0), out-of-range bytes read as zero.
-__device__ __forceinline__ pw_rsrc_t pw_rsrc(const uint8_t *base, uint32_t span) {
-    const uint64_t p = (uint64_t)(uintptr_t)base;
-    pw_rsrc_t r;
-    r.x = __builtin_amdgcn_readfirstlane((int)(uint32_t)p);
-    r.y = __builtin_amdgcn_readfirstlane((int)((uint32_t)(p >> 32) & 0xFFFFu));
-    r.z = __builtin_amdgcn_readfirstlane((int)span);
-    r.w = 0x00020000;
-    return r;
-}
-
-// Bytes s of a[0..3] -> one dword (a[0] in byte 0).
-__device__ __forceinline__ uint32_t gather4(uint32_t a0, uint32_t a1, uint32_t a2, uint32_t a3, int s) {
-    const uint32_t sel = (uint32_t)s | ((uint32_t)(s + 4) << 8) | 0x0c0c0000u;   // 0x0c: zero byte
-    const uint32_t x01 = __builtin_amdgcn_perm(a1, a0, sel), x23 = __builtin_amdgcn_perm(a3, a2, sel);
-    return __builtin_amdgcn_perm(x23, x01, 0x05040100u);
-}
-
-// ---- tile kernel (default) ---------------------------------------------------------------------
-namespace pt {
-
-constexpr int kThreads = 512;
+// ---- tile skeleton: what k_pt_lin and k_pq_lin share ---------------------------------------------
+// One workgroup of K::kWaves waves per 256-codeword tile, persistent over tiles.  A kernel is the
+// skeleton plus a policy K: its wave count and its main loop K::pass (wave W's share of the
+// positions into its state V).  Everything around the main loop is written once here: the tile's
+// LDS-DMA, the shard row table, the recursive-halving exchange, the fold, the flags and the stores.
 constexpr int kLds = 81920;                   // 80 KiB: two workgroups per CU
 constexpr int kGuard = 256;                   // bytes before the image: row 0's pad positions
 constexpr int kImage = 65536;                 // the tile image (256 rows x pitch <= 256 B)
-constexpr int kFlags = kGuard + kImage;       // decode flags [8][64] after the image
-constexpr int kTab = kFlags + 2048;           // shard batches: per-row image offset and pad [256]
+constexpr int kFlags = kGuard + kImage;       // decode flags [kWaves][64] after the image, then (shard
+                                              // batches) the per-row image offsets and pads [256]
+template <int NW> constexpr int kTabOf = kFlags + 256 * NW;   // NW = the kernel's waves
 constexpr uint32_t kOob = 0xF0000000u;        // a buffer offset past every span (ps_max_rows)
-static_assert(kTab + 1024 <= kLds, "tile kernel LDS");
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
-// The lane id, recomputed (v_mbcnt) wherever it is used: values derived from it are then not
-// hoisted out of the tile loop, where they would pin registers across the state.
-__device__ __forceinline__ uint32_t fresh(uint32_t = 0) {
-    uint32_t l;
-    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-    return l;
-}
 
 template <int N> __device__ __forceinline__ void wait_vm() {
     asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory");
@@ -199,15 +155,16 @@ template <int N> __device__ __forceinline__ void wait_vm() {
 __device__ __forceinline__ void wait_lgkm() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 __device__ __forceinline__ void barrier() { asm volatile("s_barrier" ::: "memory"); }
 
-__device__ __forceinline__ void store_dword(pw_rsrc_t r, uint32_t off, uint32_t v) {
+__device__ __forceinline__ void store_dword(rsrc_t r, uint32_t off, uint32_t v) {
     asm volatile("buffer_store_dword %0, %1, %2, 0 offen" :: "v"(v), "v"(off), "s"(r) : "memory");
 }
-__device__ __forceinline__ void store_byte(pw_rsrc_t r, uint32_t off, uint32_t v) {
+__device__ __forceinline__ void store_byte(rsrc_t r, uint32_t off, uint32_t v) {
     asm volatile("buffer_store_byte %0, %1, %2, 0 offen" :: "v"(v), "v"(off), "s"(r) : "memory");
 }
 
 // Recursive-halving exchange, sub-rounds S.. (see gen_ps.py PtRole): send the XS items to the
-// area, then add the partner's XV items.  lx = this lane's byte in wave 0's slot 0.
+// area (slots of XCAP items x 2 KiB per wave), then add the partner's XV items.  lx = this lane's
+// byte in wave 0's slot 0.
 template <class C, int W, int S, int J = 0>
 __device__ __forceinline__ void xsend(uint32_t (&V)[C::NI][8], uint32_t lx) {
     if constexpr (J < C::XCAP) {
@@ -270,19 +227,21 @@ __device__ __forceinline__ void xrecv_pipe(uint32_t (&V)[C::NI][8], uint32_t lx)
     if constexpr (J1 < C::XCAP) xread<C, PW, J1>(b, lx);
     xrecv_run<C, W, S, PW, J0>(V, lx, a, b);
 }
-template <class C, int W, int S>
+// the partner of round XR[S]: the wave of the same leader group (W mod GN, GN groups: the policy's)
+// whose position share differs in that bit
+template <class C, int GN, int W, int S>
 __device__ __forceinline__ void xrecv(uint32_t (&V)[C::NI][8], uint32_t lx) {
-    xrecv_pipe<C, W, S, W ^ (C::GN << C::XR[S])>(V, lx);
+    xrecv_pipe<C, W, S, W ^ (GN << C::XR[S])>(V, lx);
 }
-template <class C, int W, int S>
+template <class C, int GN, int W, int S>
 __device__ __forceinline__ void exchange(uint32_t (&V)[C::NI][8], uint32_t lx) {
     if constexpr (S < C::NSUB) {
         xsend<C, W, S>(V, lx);
         wait_lgkm();
         barrier();
-        xrecv<C, W, S>(V, lx);
+        xrecv<C, GN, W, S>(V, lx);
         barrier();                                           // read before the area is reused
-        exchange<C, W, S + 1>(V, lx);
+        exchange<C, GN, W, S + 1>(V, lx);
     }
 }
 
@@ -292,7 +251,7 @@ __device__ __forceinline__ void exchange(uint32_t (&V)[C::NI][8], uint32_t lx) {
 // 32 distinct LDS banks, so the row reads (ds_read2_b32, 4-byte aligned, then v_alignbyte by the
 // row's byte phase (kP - lo) mod 4) are conflict-free (an even pitch is correct, with conflicts).
 // One tile buffer per workgroup; the other workgroup on the CU computes while this one's next tile
-// lands.  The exchange uses the whole 80 KiB once the image is consumed.
+// lands.  The exchange uses the image once it is consumed.
 
 // Shard batches: byte offset (from the span base) and pad (full-frame position of the first byte)
 // of codeword k.  Row j of shard q sits at q * spitch + j * stride; a shard's last row is shortened.
@@ -314,17 +273,230 @@ __device__ __forceinline__ uint32_t sh_align(uint32_t off, uint32_t &bytes) {
     return off - mis;
 }
 
-__device__ __forceinline__ void issue_tile_lin(uint32_t lbuf, pw_rsrc_t rsrc, uint32_t toff, uint32_t tile_bytes,
-                                               int w, int ablate) {
-    if (ablate & 8) return;
+// The tile's DMA, wave w taking every NW-th 1 KiB instruction
+template <int NW>
+__device__ __forceinline__ void issue_tile(uint32_t lbuf, rsrc_t rsrc, uint32_t toff, uint32_t tile_bytes, int w) {
+#ifdef EZRS_PQ_ABL_NODMA
+    return;                                                  // timing-only builds (pq_stamps)
+#endif
     const uint32_t ninstr = (tile_bytes + 1023) >> 10;
-    const uint32_t lo16 = 16u * fresh();
-    for (uint32_t i = w; i < ninstr; i += 8)
+    const uint32_t lo16 = 16u * lane_id();
+    for (uint32_t i = (uint32_t)w; i < ninstr; i += NW)
         asm volatile("s_mov_b32 m0, %0\n\t"
                      "s_nop 0\n\t"
                      "buffer_load_dwordx4 %1, %2, 0 offen lds"
                      :: "s"(lbuf + kGuard + i * 1024u), "v"(toff + i * 1024u + lo16), "s"(rsrc) : "memory", "m0");
 }
+
+// This lane's flag word of each of the NW waves, ORed (fb: the lane's word in wave 0's row).
+template <int NW>
+__device__ __forceinline__ uint32_t read_flags(uint32_t fb) {
+    static_assert(NW == 4 || NW == 8, "flag rows");
+    uint32_t f[NW];
+    if constexpr (NW == 4) {
+        asm volatile("ds_read_b32 %0, %4\n\t"
+                     "ds_read_b32 %1, %4 offset:256\n\t"
+                     "ds_read_b32 %2, %4 offset:512\n\t"
+                     "ds_read_b32 %3, %4 offset:768\n\t"
+                     "s_waitcnt lgkmcnt(0)"
+                     : "=&v"(f[0]), "=&v"(f[1]), "=&v"(f[2]), "=&v"(f[3]) : "v"(fb) : "memory");
+        return f[0] | f[1] | f[2] | f[3];
+    } else {
+        asm volatile("ds_read_b32 %0, %8\n\t"
+                     "ds_read_b32 %1, %8 offset:256\n\t"
+                     "ds_read_b32 %2, %8 offset:512\n\t"
+                     "ds_read_b32 %3, %8 offset:768\n\t"
+                     "ds_read_b32 %4, %8 offset:1024\n\t"
+                     "ds_read_b32 %5, %8 offset:1280\n\t"
+                     "ds_read_b32 %6, %8 offset:1536\n\t"
+                     "ds_read_b32 %7, %8 offset:1792\n\t"
+                     "s_waitcnt lgkmcnt(0)"
+                     : "=&v"(f[0]), "=&v"(f[1]), "=&v"(f[2]), "=&v"(f[3]), "=&v"(f[4]),
+                       "=&v"(f[5]), "=&v"(f[6]), "=&v"(f[7]) : "v"(fb) : "memory");
+        return f[0] | f[1] | f[2] | f[3] | f[4] | f[5] | f[6] | f[7];
+    }
+}
+
+// Exchange (through the consumed image), next tile's DMA, fold and stores of wave W.
+template <class K, class C, bool ENC, int W>
+__device__ __forceinline__ void wave_tail(uint32_t (&V)[C::NI][8], const PsArgs &a, uint32_t lbuf, uint32_t tile,
+                                          uint32_t noff, uint32_t nbytes, rsrc_t rsrc, rsrc_t rout,
+                                          rsrc_t rws, int it = 0) {
+    (void)it;
+    exchange<C, K::template kGroups<C>, W, 0>(V, lbuf + 16u * lane_id());
+    TILE_STAMP(4);
+    if (noff != kOob) issue_tile<K::kWaves>(lbuf, rsrc, noff, nbytes, W);
+    uint32_t T[C::NOWN][8];
+#pragma unroll
+    for (int i = 0; i < C::NOWN; ++i)
+#pragma unroll
+        for (int t = 0; t < 8; ++t) T[i][t] = C::OWN[W][i] >= 0 ? V[C::OWN[W][i] < 0 ? 0 : C::OWN[W][i]][t] : 0u;
+    uint32_t Qs[C::NQ][8], nz = 0;
+    C::template epilogue<W>(T, [&](auto qc, uint32_t (&Qw)[8]) {
+        constexpr int qd = decltype(qc)::value;
+        constexpr uint32_t vm = (C::SYN[W][qd][0] >= 0 ? 0x01010101u : 0u) | (C::SYN[W][qd][1] >= 0 ? 0x02020202u : 0u) |
+                                (C::SYN[W][qd][2] >= 0 ? 0x04040404u : 0u) | (C::SYN[W][qd][3] >= 0 ? 0x08080808u : 0u);
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            nz |= Qw[t] & vm;
+            Qs[qd][t] = Qw[t];
+        }
+    }, [](auto) {});
+    TILE_STAMP(5);
+    const uint32_t cw0 = tile * kTile + 4u * lane_id();        // byte k <-> codeword cw0 + k
+    if constexpr (ENC) {
+        // syndrome-major workspace in codeword order: the dword at column cw0 holds cw0 .. cw0+3
+        static_for<0, C::NQ>([&](auto qc) {
+            constexpr int qd = decltype(qc)::value;
+            transpose8(Qs[qd]);                              // Qs[qd][jj] byte k: syndrome jj, codeword k
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj)
+                if (C::SYN[W][qd][jj] >= 0)
+                    store_dword(rws, (uint32_t)(C::SYN[W][qd][jj] * a.ws_pitch) + cw0, Qs[qd][jj]);
+        });
+    } else {
+        uint32_t fl = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (nz >> (8 * k) & 0xFF) fl |= 1u << k;
+        const uint32_t fa = lbuf + kFlags + 256u * W + 4u * lane_id();
+        asm volatile("ds_write_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" :: "v"(fa), "v"(fl) : "memory");
+        barrier();
+        fl = read_flags<K::kWaves>(lbuf + kFlags + 4u * lane_id());
+        if constexpr (W == 0) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                store_dword(rout, (cw0 + k) * 4u, (fl >> k & 1) ? (uint32_t)kSentinel : 0u);
+            if (fl != 0 && a.flag) *a.flag = a.gen;          // this call flagged a codeword
+        }
+        if (__ballot(fl != 0) != 0) {                        // flagged codewords: their syndromes
+            static_for<0, C::NQ>([&](auto qc) {
+                constexpr int qd = decltype(qc)::value;
+                transpose8(Qs[qd]);
+                // tiled layout (ezrs_internal.hpp kSynTile): syndrome j of the 256 codewords of a tile
+                // in one 256-byte row, so a lane's four codewords are one dword (unflagged ones included)
+                if (a.ws_pitch == 0) {
+#pragma unroll
+                    for (int jj = 0; jj < 4; ++jj)
+                        if (C::SYN[W][qd][jj] >= 0)
+                            store_dword(rws, tile * (uint32_t)kSynTile + 256u * C::SYN[W][qd][jj] + 4u * lane_id(),
+                                        Qs[qd][jj]);
+                } else {                                     // a launch not starting a tile (shards)
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const uint32_t g = (uint32_t)a.ws_pitch + cw0 + k;
+                        const uint32_t row = (fl >> k & 1) ? (g >> 8) * (uint32_t)kSynTile + (g & 255u) : kOob;
+#pragma unroll
+                        for (int jj = 0; jj < 4; ++jj)
+                            if (C::SYN[W][qd][jj] >= 0)
+                                store_byte(rws, row + 256u * C::SYN[W][qd][jj], Qs[qd][jj] >> (8 * k));
+                    }
+                }
+            });
+        }
+    }
+}
+
+// Wave W of a workgroup, persistent over the tiles blockIdx.x, blockIdx.x + gridDim.x, ...
+template <class K, class C, bool ENC, int W, bool SH, bool LO0>
+__device__ __forceinline__ void tile_run(const PsArgs &a, uint8_t *lds) {
+    constexpr uint32_t RW = kTile / K::kWaves;               // rows of the shard row table per wave
+    const rsrc_t rsrc = make_rsrc(a.base, a.span);
+    const uint32_t lbuf = __builtin_amdgcn_readfirstlane(lds_addr(lds));
+    const rsrc_t rout = make_rsrc(reinterpret_cast<const uint8_t *>(a.result), ENC ? 0u : a.ncw * 4u);
+    const rsrc_t rws = make_rsrc(a.ws, ENC ? (uint32_t)(C::NR * a.ws_pitch)
+                                            : (uint32_t)((a.ws_pitch + a.ncw + 255) / 256 * kSynTile));
+    // byte range of tile t: plain batches t * 256 rows of pitch stride; shard batches from its first
+    // row's start to the next tile's (the span's end for the last tile)
+    auto tile_range = [&](uint32_t t, uint32_t &bytes) -> uint32_t {
+        if (!SH) {
+            bytes = a.stride * kTile;
+            return t * bytes;
+        }
+        int lo;
+        const uint32_t t0 = t * kTile, off = row_at(a, t0, lo);
+        bytes = (t0 + kTile < a.ncw ? row_at(a, t0 + kTile, lo) : a.span) - off;
+        return sh_align(off, bytes);
+    };
+    uint32_t tile = blockIdx.x;
+    TILE_RT(0);
+    uint32_t tbytes, toff = tile < a.ntiles ? tile_range(tile, tbytes) : 0u;
+    if (tile < a.ntiles) issue_tile<K::kWaves>(lbuf, rsrc, toff, tbytes, W);
+    int it = 0;
+    (void)it;
+    for (; tile < a.ntiles; tile += gridDim.x, ++it) {
+        TILE_STAMP(0);
+        // run-time values re-read each tile: nothing derived from them is hoisted out of the loop
+        int lo = a.lo;
+        asm volatile("" : "+s"(lo));
+        uint32_t nbytes = 0;
+        const uint32_t noff = tile + gridDim.x < a.ntiles ? tile_range(tile + gridDim.x, nbytes) : kOob;
+        uint32_t V[C::NI][8];                                // set by the wave's first block
+        wait_vm<0>();                                        // the tile landed (and the stores went)
+        if constexpr (SH) {                                  // row table: wave W writes rows RW * W ..
+            const uint32_t j = lane_id();
+            if (RW == 64 || j < RW) {
+                const uint32_t r = RW * (uint32_t)W + j, k = tile * kTile + r;
+                uint32_t e = kGuard;
+                if (k < a.ncw) {
+                    int rlo;
+                    const uint32_t at = row_at(a, k, rlo);
+                    e = (kGuard + at - toff - (uint32_t)rlo) | ((uint32_t)rlo << 24);
+                }
+                asm volatile("ds_write_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" :: "v"(lbuf + kTabOf<K::kWaves> + 4u * r), "v"(e) : "memory");
+            }
+        }
+        barrier();
+        if (toff + tbytes >= a.span) {                       // last tile: the span's final bytes
+            // a 16-byte DMA piece that crosses the span's end comes back all-zero: re-read the last
+            // 64 bytes one by one (out-of-range bytes read as zero)
+            if (W == 0) {
+                const uint32_t off = a.span - 64u + lane_id();
+                uint32_t v;
+                asm volatile("buffer_load_ubyte %0, %1, %2, 0 offen\n\ts_waitcnt vmcnt(0)"
+                             : "=&v"(v) : "v"(off), "s"(rsrc) : "memory");
+                if (off >= toff && off < a.span)
+                    asm volatile("ds_write_b8 %0, %1\n\ts_waitcnt lgkmcnt(0)"
+                                 :: "v"(lbuf + kGuard + (off - toff)), "v"(v) : "memory");
+            }
+            barrier();
+        }
+        int tlo = lo;                                        // shard batches: pad of the tile's rows
+        if constexpr (SH) {
+            const uint32_t t0 = tile * kTile, kt = (t0 / a.srows) * a.srows + a.srows - 1;
+            if (kt < t0 + kTile && kt < a.ncw) tlo = a.stail_lo;
+        }
+        TILE_STAMP(1);
+        // the main loop outranks the other workgroup's waves on the SIMD (their exchange, DMA and
+        // fold): r04j C2 1203 vs 1169 GB/s; r06c: tails over main loops 1503, equal priority 1430,
+        // main loops over tails 1558 GB/s (profiles/r06/r06c_priority_ab.txt); r04k on k_pt_lin
+        // 1115 vs 1091 GB/s
+        asm volatile("s_setprio 1");
+        K::template pass<C, ENC, W, SH, LO0>(V, lbuf, a.stride, lo, tlo);
+        asm volatile("s_setprio 0");
+        TILE_STAMP(2);
+        barrier();                                           // the image is consumed
+        TILE_STAMP(3);
+        wave_tail<K, C, ENC, W>(V, a, lbuf, tile, noff, nbytes, rsrc, rout, rws, it);
+        TILE_STAMP(6);
+        toff = noff;
+        tbytes = nbytes;
+    }
+    wait_vm<0>();                                            // no DMA may land after the exit
+    TILE_RT(1);
+}
+
+// ---- 8-wave tile kernel k_pt_lin (PT_<codec>, codegen gen_pt) -----------------------------------
+// One 512-thread workgroup (8 waves) per tile, <= 128 VGPRs (4 waves per SIMD).  Waves split the
+// leaders into GN groups and the 16-position pieces into QN = 8 / GN quarters; wave (g, q) reads
+// its quarter's pieces and runs each piece's own networks for group g's leaders.  The exchange then
+// leaves every wave the totals of the leaders whose quad of syndromes (NQ = 1) it folds.
+namespace pt {
+
+constexpr int kWaves = 8;
+constexpr int kThreads = 64 * kWaves;
+constexpr int kTab = kTabOf<kWaves>;          // flags [8][64], then the row table
+static_assert(kTab + 1024 <= kLds, "tile kernel LDS");
 
 // Positions pa .. pa+7 (words X) with the network of quarter 0's block B0; positions before lo
 // (the zero pad of a shortened code: the image holds the previous row's bytes there) and at or
@@ -353,7 +525,7 @@ __device__ __forceinline__ void block8_rt(uint32_t (&V)[C::NI][8], uint32_t (&X)
 // Rows 4l + k, positions pa .. pa+15 (k = 0..3): R[k] = 16 bytes of row k.
 __device__ __forceinline__ void read_rows_lin(u32x4 (&R)[4], uint32_t lbuf, uint32_t stride, int pa, int lo,
                                               const uint32_t (&ph)[4]) {
-    const uint32_t base = lbuf + kGuard + 4u * fresh() * stride + (uint32_t)(pa - lo);
+    const uint32_t base = lbuf + kGuard + 4u * lane_id() * stride + (uint32_t)(pa - lo);
     u32x2 e[4][2];
     uint32_t d4[4];
 #pragma unroll
@@ -424,7 +596,7 @@ __device__ __forceinline__ void lin_pass(uint32_t (&V)[C::NI][8], uint32_t lbuf,
     static_assert(16 * (C::PIECE[G][0] + Q) < HI, "the wave's first block sets its state");
     u32x4 e = {0, 0, 0, 0};
     if constexpr (SH)
-        asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(e) : "v"(lbuf + kTab + 16u * fresh()) : "memory");
+        asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(e) : "v"(lbuf + kTab + 16u * lane_id()) : "memory");
     static_for<0, NP>([&](auto Ic) {
         constexpr int I = decltype(Ic)::value;
         constexpr int p0 = C::PIECE[G][I];
@@ -454,204 +626,38 @@ __device__ __forceinline__ void lin_pass(uint32_t (&V)[C::NI][8], uint32_t lbuf,
     });
 }
 
-// Fix-up, exchange (through the consumed image), next tile's DMA, fold and stores of wave W.
-template <class C, bool ENC, int W>
-__device__ __forceinline__ void wave_tail_lin(uint32_t (&V)[C::NI][8], const PsArgs &a, uint32_t lbuf,
-                                              uint32_t tile, uint32_t noff, uint32_t nbytes,
-                                              pw_rsrc_t rsrc, pw_rsrc_t rout, pw_rsrc_t rws, int pt_it = 0) {
-    const int pt_w = W;
-    (void)pt_it; (void)pt_w;
-    constexpr int G = W % C::GN, Q = W / C::GN;
-    if (!(a.ablate & 2)) {
-        exchange<C, W, 0>(V, lbuf + 16u * fresh());         // slot (W XCAP + j) at 2 KiB each
-    }
-    PT_STAMP(4);
-    if (noff != kOob) issue_tile_lin(lbuf, rsrc, noff, nbytes, W, a.ablate);
-    uint32_t T[C::NOWN][8];
-#pragma unroll
-    for (int i = 0; i < C::NOWN; ++i)
-#pragma unroll
-        for (int t = 0; t < 8; ++t) T[i][t] = C::OWN[W][i] >= 0 ? V[C::OWN[W][i] < 0 ? 0 : C::OWN[W][i]][t] : 0u;
-    uint32_t Qs[8] = {0, 0, 0, 0, 0, 0, 0, 0}, nz = 0;
-    constexpr uint32_t vm = (C::SYN[W][0][0] >= 0 ? 0x01010101u : 0u) | (C::SYN[W][0][1] >= 0 ? 0x02020202u : 0u) |
-                            (C::SYN[W][0][2] >= 0 ? 0x04040404u : 0u) | (C::SYN[W][0][3] >= 0 ? 0x08080808u : 0u);
-    if (!(a.ablate & 4))
-        C::template epilogue<W>(T, [&](auto, uint32_t (&Qw)[8]) {
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                nz |= Qw[t] & vm;
-                Qs[t] = Qw[t];
-            }
-        }, [](auto) {});
-    PT_STAMP(5);
-    const uint32_t cw0 = tile * kTile + 4u * fresh();        // byte k <-> codeword cw0 + k
-    if constexpr (ENC) {
-        transpose8(Qs);                                      // Qs[jj] byte k: syndrome jj, codeword k
-        // syndrome-major workspace in codeword order: the dword at column cw0 holds cw0 .. cw0+3
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj)
-            if (C::SYN[W][0][jj] >= 0) store_dword(rws, (uint32_t)(C::SYN[W][0][jj] * a.ws_pitch) + cw0, Qs[jj]);
-    } else {
-        uint32_t fl = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (nz >> (8 * k) & 0xFF) fl |= 1u << k;
-        const uint32_t fa = lbuf + kFlags + 256u * W + 4u * fresh();
-        asm volatile("ds_write_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" :: "v"(fa), "v"(fl) : "memory");
-        barrier();
-        {
-            uint32_t f[8];
-            const uint32_t fb = lbuf + kFlags + 4u * fresh();
-            asm volatile("ds_read_b32 %0, %8\n\t"
-                         "ds_read_b32 %1, %8 offset:256\n\t"
-                         "ds_read_b32 %2, %8 offset:512\n\t"
-                         "ds_read_b32 %3, %8 offset:768\n\t"
-                         "ds_read_b32 %4, %8 offset:1024\n\t"
-                         "ds_read_b32 %5, %8 offset:1280\n\t"
-                         "ds_read_b32 %6, %8 offset:1536\n\t"
-                         "ds_read_b32 %7, %8 offset:1792\n\t"
-                         "s_waitcnt lgkmcnt(0)"
-                         : "=&v"(f[0]), "=&v"(f[1]), "=&v"(f[2]), "=&v"(f[3]), "=&v"(f[4]),
-                           "=&v"(f[5]), "=&v"(f[6]), "=&v"(f[7]) : "v"(fb) : "memory");
-            fl = f[0] | f[1] | f[2] | f[3] | f[4] | f[5] | f[6] | f[7];
-            if (a.ablate & 32) fl = 0;                       // timing runs: keep the error path idle
-        }
-        if constexpr (W == 0) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                store_dword(rout, (cw0 + k) * 4u, (fl >> k & 1) ? (uint32_t)kSentinel : 0u);
-            if (fl != 0 && a.flag) *a.flag = a.gen;          // this call flagged a codeword
-        }
-        if (__ballot(fl != 0) != 0) {                        // flagged codewords: their syndromes
-            transpose8(Qs);                                  // Qs[jj] byte k: syndrome jj, codeword k
-            // tiled layout (ezrs_internal.hpp kSynTile): syndrome j of the 256 codewords of a tile in
-            // one 256-byte row, so a lane's four codewords are one dword (unflagged ones included)
-            if (a.ws_pitch == 0) {
-#pragma unroll
-                for (int jj = 0; jj < 4; ++jj)
-                    if (C::SYN[W][0][jj] >= 0)
-                        store_dword(rws, tile * (uint32_t)kSynTile + 256u * C::SYN[W][0][jj] + 4u * fresh(),
-                                    Qs[jj]);
-            } else {                                         // a launch not starting a tile (shards)
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const uint32_t g = (uint32_t)a.ws_pitch + cw0 + k;
-                    const uint32_t row = (fl >> k & 1) ? (g >> 8) * (uint32_t)kSynTile + (g & 255u) : kOob;
-#pragma unroll
-                    for (int jj = 0; jj < 4; ++jj)
-                        if (C::SYN[W][0][jj] >= 0) store_byte(rws, row + 256u * C::SYN[W][0][jj], Qs[jj] >> (8 * k));
-                }
-            }
-        }
-    }
-    PT_STAMP(6);
-}
-
-template <class C, bool ENC, int W, bool SH, bool LO0>
-__device__ __forceinline__ void pt_run_lin(const PsArgs &a, uint8_t *lds) {
-    constexpr int G = W % C::GN, Q = W / C::GN;
-    const int w = W;
-    constexpr int HI = ENC ? kN - (int)C::NR : kN;
-    const pw_rsrc_t rsrc = pw_rsrc(a.base, a.span);
-    const uint32_t lbuf = __builtin_amdgcn_readfirstlane(lds_addr(lds));
-    const pw_rsrc_t rout = pw_rsrc(reinterpret_cast<const uint8_t *>(a.result), ENC ? 0u : a.ncw * 4u);
-    const pw_rsrc_t rws = pw_rsrc(a.ws, ENC ? (uint32_t)(C::NR * a.ws_pitch)
-                                            : (uint32_t)((a.ws_pitch + a.ncw + 255) / 256 * kSynTile));
-    constexpr bool shards = SH;
-    // byte range of tile t: plain batches t * 256 rows of pitch stride; shard batches from its first
-    // row's start to the next tile's (the span's end for the last tile)
-    auto tile_range = [&](uint32_t t, uint32_t &bytes) -> uint32_t {
-        if (!shards) {
-            bytes = a.stride * kTile;
-            return t * bytes;
-        }
-        int lo;
-        const uint32_t t0 = t * kTile, off = row_at(a, t0, lo);
-        bytes = (t0 + kTile < a.ncw ? row_at(a, t0 + kTile, lo) : a.span) - off;
-        return sh_align(off, bytes);
-    };
-    uint32_t tile = blockIdx.x;
-    uint32_t tbytes, toff = tile < a.ntiles ? tile_range(tile, tbytes) : 0u;
-    if (tile < a.ntiles) issue_tile_lin(lbuf, rsrc, toff, tbytes, w, a.ablate);
-    int pt_it = 0, pt_w = w;
-    (void)pt_it; (void)pt_w;
-    for (; tile < a.ntiles; tile += gridDim.x, ++pt_it) {
-        // run-time values re-read each tile: nothing derived from them is hoisted out of the loop
-        int lo = a.lo;
-        asm volatile("" : "+s"(lo));
+// The skeleton's policy: wave W = quarter W / GN of leader group W % GN.
+struct Tile {
+    static constexpr int kWaves = pt::kWaves;
+    template <class C> static constexpr int kGroups = C::GN;
+    template <class C, bool ENC, int W, bool SH, bool LO0>
+    static __device__ __forceinline__ void pass(uint32_t (&V)[C::NI][8], uint32_t lbuf, uint32_t stride, int lo,
+                                                int tail_lo) {
+        constexpr int HI = ENC ? kN - (int)C::NR : kN;
         uint32_t ph[4];                                      // byte phase of row k's start
 #pragma unroll
-        for (int k = 0; k < 4; ++k) ph[k] = (lbuf + kGuard + k * a.stride - (uint32_t)lo) & 3u;
-        uint32_t nbytes = 0;
-        const uint32_t noff = tile + gridDim.x < a.ntiles ? tile_range(tile + gridDim.x, nbytes) : kOob;
-        uint32_t V[C::NI][8];                                // set by the wave's first block
-        PT_STAMP(0);
-        wait_vm<0>();                                        // the tile landed (and the stores went)
-        if constexpr (SH) {                                  // row table: wave w writes rows 32w ..
-            const uint32_t j = fresh();
-            if (j < 32u) {
-                const uint32_t r = 32u * (uint32_t)w + j, k = tile * kTile + r;
-                uint32_t e = kGuard;
-                if (k < a.ncw) {
-                    int rlo;
-                    const uint32_t at = row_at(a, k, rlo);
-                    e = (kGuard + at - toff - (uint32_t)rlo) | ((uint32_t)rlo << 24);
-                }
-                asm volatile("ds_write_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" :: "v"(lbuf + kTab + 4u * r), "v"(e) : "memory");
-            }
-        }
-        barrier();
-        PT_STAMP(1);
-        if (toff + tbytes >= a.span) {                       // last tile: the span's final bytes
-            // a 16-byte DMA piece that crosses the span's end comes back all-zero: re-read the last
-            // 64 bytes one by one (out-of-range bytes read as zero)
-            if (w == 0) {
-                const uint32_t off = a.span - 64u + fresh();
-                uint32_t v;
-                asm volatile("buffer_load_ubyte %0, %1, %2, 0 offen\n\ts_waitcnt vmcnt(0)"
-                             : "=&v"(v) : "v"(off), "s"(rsrc) : "memory");
-                if (off >= toff && off < a.span)
-                    asm volatile("ds_write_b8 %0, %1\n\ts_waitcnt lgkmcnt(0)"
-                                 :: "v"(lbuf + kGuard + (off - toff)), "v"(v) : "memory");
-            }
-            barrier();
-        }
-        // every main loop over the other workgroup's tails (r04k C2 on k_pt_lin 1115 vs 1091 GB/s)
-        asm volatile("s_setprio 1");
-        int tlo = lo;                                        // shard batches: pad of the tile's rows
-        if constexpr (SH) {
-            const uint32_t t0 = tile * kTile, kt = (t0 / a.srows) * a.srows + a.srows - 1;
-            if (kt < t0 + kTile && kt < a.ncw) tlo = a.stail_lo;
-        }
-        lin_pass<C, G, Q, HI, SH, LO0>(V, lbuf, a.stride, lo, ph, tlo);
-        asm volatile("s_setprio 0");
-        PT_STAMP(2);
-        barrier();                                           // the image is consumed
-        PT_STAMP(3);
-        wave_tail_lin<C, ENC, W>(V, a, lbuf, tile, noff, nbytes, rsrc, rout, rws, pt_it);
-        toff = noff;
-        tbytes = nbytes;
+        for (int k = 0; k < 4; ++k) ph[k] = (lbuf + kGuard + k * stride - (uint32_t)lo) & 3u;
+        lin_pass<C, W % C::GN, W / C::GN, HI, SH, LO0>(V, lbuf, stride, lo, ph, tail_lo);
     }
-    wait_vm<0>();                                            // no DMA may land after the exit
-}
+};
 
 template <class C, bool ENC, bool SH, bool LO0>
 __global__ void __attribute__((amdgpu_flat_work_group_size(kThreads, kThreads), amdgpu_waves_per_eu(4)))
 k_pt_lin(PsArgs a) {
     static_assert(C::NQ == 1, "one quad (4 syndromes) per wave");
-    static_assert(C::GN <= 2 && C::GN * C::QN == 8, "8 waves: at most two leader groups");
-    static_assert(8 * C::XCAP * 2048 <= kLds, "exchange area");
+    static_assert(C::GN <= 2 && C::GN * C::QN == kWaves, "8 waves: at most two leader groups");
+    static_assert(kWaves * C::XCAP * 2048 <= kLds, "exchange area");
     __shared__ __attribute__((aligned(16))) uint8_t lds[kLds];
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     switch (w) {                                             // each wave's pieces and tail, compiled
-    case 0: pt_run_lin<C, ENC, 0, SH, LO0>(a, lds); break;
-    case 1: pt_run_lin<C, ENC, 1, SH, LO0>(a, lds); break;
-    case 2: pt_run_lin<C, ENC, 2, SH, LO0>(a, lds); break;
-    case 3: pt_run_lin<C, ENC, 3, SH, LO0>(a, lds); break;
-    case 4: pt_run_lin<C, ENC, 4, SH, LO0>(a, lds); break;
-    case 5: pt_run_lin<C, ENC, 5, SH, LO0>(a, lds); break;
-    case 6: pt_run_lin<C, ENC, 6, SH, LO0>(a, lds); break;
-    default: pt_run_lin<C, ENC, 7, SH, LO0>(a, lds); break;
+    case 0: tile_run<Tile, C, ENC, 0, SH, LO0>(a, lds); break;
+    case 1: tile_run<Tile, C, ENC, 1, SH, LO0>(a, lds); break;
+    case 2: tile_run<Tile, C, ENC, 2, SH, LO0>(a, lds); break;
+    case 3: tile_run<Tile, C, ENC, 3, SH, LO0>(a, lds); break;
+    case 4: tile_run<Tile, C, ENC, 4, SH, LO0>(a, lds); break;
+    case 5: tile_run<Tile, C, ENC, 5, SH, LO0>(a, lds); break;
+    case 6: tile_run<Tile, C, ENC, 6, SH, LO0>(a, lds); break;
+    default: tile_run<Tile, C, ENC, 7, SH, LO0>(a, lds); break;
     }
 }
 
@@ -661,45 +667,18 @@ k_pt_lin(PsArgs a) {
 // One 256-thread workgroup (4 waves) per 256-codeword tile, two workgroups per CU (80 KiB LDS
 // each), up to 256 VGPRs (2 waves per SIMD).  Wave W evaluates EVERY coset leader (NI x 8 state
 // words) over its own contiguous run of 8-position blocks with each block's own network: the
-// tile's rows are read and their Four-Russians combinations formed once (the 8-wave kernel reads
-// every position twice, once per leader group, and fixes up three quarters by alpha^(-16 q e)).
-// The next piece's LDS reads are in flight while the current piece's networks run.  Then a
-// two-round recursive-halving exchange through the consumed image leaves each wave the totals of
-// the leaders whose two quads of syndromes it folds.  Image, DMA, flags and stores as k_pt_lin.
+// tile's rows are read and their Four-Russians combinations formed once (the 8-wave kernel with
+// two leader groups reads every position twice, once per group).
+// The next piece's LDS reads are in flight while the current piece's networks run.  Then the
+// skeleton's two-round exchange leaves each wave the totals of the leaders whose (up to two) quads
+// of syndromes it folds.
 namespace pq {
 
-using pt::kGuard;
-using pt::kImage;
-using pt::kOob;
-using pt::u32x2;
-using pt::u32x4;
-constexpr int kThreads = 256;
 constexpr int kWaves = 4;
-constexpr int kLds = 81920;                   // 80 KiB: two workgroups per CU
-constexpr int kFlags = kGuard + kImage;       // decode flags [4][64] after the image
-constexpr int kTab = kFlags + 1024;           // shard batches: per-row image offset and pad [256]
+constexpr int kThreads = 64 * kWaves;
+constexpr int kTab = kTabOf<kWaves>;          // flags [4][64], then the row table
 static_assert(kTab + 1024 <= kLds, "pq tile kernel LDS");
 
-// Raw dwords of rows 4l + k at one 16-position piece (4-byte aligned reads, aligned afterwards).
-struct Raw {
-    u32x2 e[4][2];
-    uint32_t d4[4];
-};
-
-// the piece at byte offset OFF (a multiple of 8) from the rows' dword-aligned position-0 addresses
-// at4[k]: the offset rides in the instructions' immediates
-template <int OFF>
-__device__ __forceinline__ void issue_at(Raw &r, const uint32_t (&at4)[4]) {
-    static_assert(OFF % 4 == 0 && OFF / 4 + 4 < 256, "ds_read2 dword offsets");
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        asm volatile("ds_read2_b32 %0, %3 offset0:%4 offset1:%5\n\t"
-                     "ds_read2_b32 %1, %3 offset0:%6 offset1:%7\n\t"
-                     "ds_read_b32 %2, %3 offset:%8"
-                     : "=&v"(r.e[k][0]), "=&v"(r.e[k][1]), "=&v"(r.d4[k])
-                     : "v"(at4[k]), "n"(OFF / 4), "n"(OFF / 4 + 1), "n"(OFF / 4 + 2), "n"(OFF / 4 + 3), "n"(OFF + 16)
-                     : "memory");
-}
 // a final single-block piece: bytes OFF .. OFF+11 only (the dwords block B+1 would need are not
 // read, so no dead in-flight register is left for the allocator to move)
 template <int OFF>
@@ -718,12 +697,6 @@ __device__ __forceinline__ void issue_piece(Raw &r, const uint32_t (&at4)[4]) {
     if constexpr (HALF) issue_half<OFF>(r, at4);
     else issue_at<OFF>(r, at4);
 }
-__device__ __forceinline__ void wait_raw(Raw &r) {
-    asm volatile("s_waitcnt lgkmcnt(0)"
-                 : "+v"(r.e[0][0]), "+v"(r.e[0][1]), "+v"(r.d4[0]), "+v"(r.e[1][0]), "+v"(r.e[1][1]), "+v"(r.d4[1]),
-                   "+v"(r.e[2][0]), "+v"(r.e[2][1]), "+v"(r.d4[2]), "+v"(r.e[3][0]), "+v"(r.e[3][1]), "+v"(r.d4[3])
-                 :: "memory");
-}
 // byte address of row 4l + k at position 0 (plain batches: packed rows of pitch `stride`, the
 // first byte at position lo; shard batches: the row-table entry e[k] = image offset of position 0 |
 // pad << 24)
@@ -732,7 +705,7 @@ __device__ __forceinline__ void row_addrs(uint32_t (&at)[4], uint32_t lbuf, uint
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         if constexpr (SH) at[k] = lbuf + (e[k] & 0xFFFFFFu);
-        else at[k] = lbuf + kGuard + (4u * pt::fresh() + k) * stride - (uint32_t)lo;
+        else at[k] = lbuf + kGuard + (4u * lane_id() + k) * stride - (uint32_t)lo;
     }
 }
 // aligned 16 bytes of each row; shard batches: bytes before a shortened row's own pad masked off
@@ -831,7 +804,7 @@ __device__ __forceinline__ void pq_pass(uint32_t (&V)[C::NI][8], uint32_t lbuf, 
     constexpr int b0 = C::B0[E][W];
     u32x4 e = {0, 0, 0, 0};
     if constexpr (SH)
-        asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(e) : "v"(lbuf + kTab + 16u * pt::fresh()) : "memory");
+        asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(e) : "v"(lbuf + kTab + 16u * lane_id()) : "memory");
     Raw cur;
     uint32_t at[4], at4[4];
     row_addrs<SH>(at, lbuf, stride, lo, e);
@@ -845,216 +818,16 @@ __device__ __forceinline__ void pq_pass(uint32_t (&V)[C::NI][8], uint32_t lbuf, 
     piece<C, ENC, W, SH, LO0, 0>(V, cur, at, at4, lo, tail_lo, pads);
 }
 
-// Recursive-halving exchange (partner W ^ (1 << XR[s])), slots of XCAP items x 2 KiB per wave.
-template <class C, int W, int S, int J = 0>
-__device__ __forceinline__ void xsend(uint32_t (&V)[C::NI][8], uint32_t lx) {
-    if constexpr (J < C::XCAP) {
-        constexpr int it = C::XS[W][S][J];
-        if constexpr (it >= 0) {
-            const u32x4 w0 = {V[it][0], V[it][1], V[it][2], V[it][3]};
-            const u32x4 w1 = {V[it][4], V[it][5], V[it][6], V[it][7]};
-            asm volatile("ds_write_b128 %0, %1 offset:%3\n\t"
-                         "ds_write_b128 %0, %2 offset:%4"
-                         :: "v"(lx + W * C::XCAP * 2048u), "v"(w0), "v"(w1), "n"(J * 2048),
-                            "n"(J * 2048 + 1024) : "memory");
-        }
-        xsend<C, W, S, J + 1>(V, lx);
+// The skeleton's policy: wave W = run W of the positions, every leader.
+struct Tile {
+    static constexpr int kWaves = pq::kWaves;
+    template <class C> static constexpr int kGroups = 1;    // every leader in every wave
+    template <class C, bool ENC, int W, bool SH, bool LO0>
+    static __device__ __forceinline__ void pass(uint32_t (&V)[C::NI][8], uint32_t lbuf, uint32_t stride, int lo,
+                                                int tail_lo) {
+        pq_pass<C, ENC, W, SH, LO0>(V, lbuf, stride, lo, tail_lo);
     }
-}
-template <class C, int W, int S>
-__device__ __forceinline__ void xrecv(uint32_t (&V)[C::NI][8], uint32_t lx) {
-    pt::xrecv_pipe<C, W, S, W ^ (1 << C::XR[S])>(V, lx);
-}
-template <class C, int W, int S>
-__device__ __forceinline__ void exchange(uint32_t (&V)[C::NI][8], uint32_t lx) {
-    if constexpr (S < C::NSUB) {
-        xsend<C, W, S>(V, lx);
-        pt::wait_lgkm();
-        pt::barrier();
-        xrecv<C, W, S>(V, lx);
-        pt::barrier();                                       // read before the area is reused
-        exchange<C, W, S + 1>(V, lx);
-    }
-}
-
-// The tile's DMA, wave w taking every fourth 1 KiB instruction
-__device__ __forceinline__ void issue_tile(uint32_t lbuf, pw_rsrc_t rsrc, uint32_t toff, uint32_t tile_bytes, int w) {
-#ifdef EZRS_PQ_ABL_NODMA
-    return;                                                  // timing-only builds (pq_stamps)
-#endif
-    const uint32_t ninstr = (tile_bytes + 1023) >> 10;
-    const uint32_t lo16 = 16u * pt::fresh();
-    for (uint32_t i = (uint32_t)w; i < ninstr; i += kWaves)
-        asm volatile("s_mov_b32 m0, %0\n\t"
-                     "s_nop 0\n\t"
-                     "buffer_load_dwordx4 %1, %2, 0 offen lds"
-                     :: "s"(lbuf + kGuard + i * 1024u), "v"(toff + i * 1024u + lo16), "s"(rsrc) : "memory", "m0");
-}
-
-// Exchange, next tile's DMA, fold and stores of wave W.
-template <class C, bool ENC, int W>
-__device__ __forceinline__ void wave_tail(uint32_t (&V)[C::NI][8], const PsArgs &a, uint32_t lbuf, uint32_t tile,
-                                          uint32_t noff, uint32_t nbytes, pw_rsrc_t rsrc, pw_rsrc_t rout,
-                                          pw_rsrc_t rws, int pq_it = 0) {
-    (void)pq_it;
-    exchange<C, W, 0>(V, lbuf + 16u * pt::fresh());
-    PQ_STAMP(4);
-    if (noff != kOob) issue_tile(lbuf, rsrc, noff, nbytes, W);
-    uint32_t T[C::NOWN][8];
-#pragma unroll
-    for (int i = 0; i < C::NOWN; ++i)
-#pragma unroll
-        for (int t = 0; t < 8; ++t) T[i][t] = C::OWN[W][i] >= 0 ? V[C::OWN[W][i] < 0 ? 0 : C::OWN[W][i]][t] : 0u;
-    uint32_t Qs[C::NQ][8], nz = 0;
-    C::template epilogue<W>(T, [&](auto qc, uint32_t (&Qw)[8]) {
-        constexpr int qd = decltype(qc)::value;
-        constexpr uint32_t vm = (C::SYN[W][qd][0] >= 0 ? 0x01010101u : 0u) | (C::SYN[W][qd][1] >= 0 ? 0x02020202u : 0u) |
-                                (C::SYN[W][qd][2] >= 0 ? 0x04040404u : 0u) | (C::SYN[W][qd][3] >= 0 ? 0x08080808u : 0u);
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            nz |= Qw[t] & vm;
-            Qs[qd][t] = Qw[t];
-        }
-    }, [](auto) {});
-    PQ_STAMP(5);
-    const uint32_t cw0 = tile * kTile + 4u * pt::fresh();    // byte k <-> codeword cw0 + k
-    if constexpr (ENC) {
-        static_for<0, C::NQ>([&](auto qc) {
-            constexpr int qd = decltype(qc)::value;
-            transpose8(Qs[qd]);                              // Qs[qd][jj] byte k: syndrome jj, codeword k
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj)
-                if (C::SYN[W][qd][jj] >= 0)
-                    pt::store_dword(rws, (uint32_t)(C::SYN[W][qd][jj] * a.ws_pitch) + cw0, Qs[qd][jj]);
-        });
-    } else {
-        uint32_t fl = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (nz >> (8 * k) & 0xFF) fl |= 1u << k;
-        const uint32_t fa = lbuf + kFlags + 256u * W + 4u * pt::fresh();
-        asm volatile("ds_write_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" :: "v"(fa), "v"(fl) : "memory");
-        pt::barrier();
-        {
-            uint32_t f[4];
-            const uint32_t fb = lbuf + kFlags + 4u * pt::fresh();
-            asm volatile("ds_read_b32 %0, %4\n\t"
-                         "ds_read_b32 %1, %4 offset:256\n\t"
-                         "ds_read_b32 %2, %4 offset:512\n\t"
-                         "ds_read_b32 %3, %4 offset:768\n\t"
-                         "s_waitcnt lgkmcnt(0)"
-                         : "=&v"(f[0]), "=&v"(f[1]), "=&v"(f[2]), "=&v"(f[3]) : "v"(fb) : "memory");
-            fl = f[0] | f[1] | f[2] | f[3];
-        }
-        if constexpr (W == 0) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                pt::store_dword(rout, (cw0 + k) * 4u, (fl >> k & 1) ? (uint32_t)kSentinel : 0u);
-            if (fl != 0 && a.flag) *a.flag = a.gen;          // this call flagged a codeword
-        }
-        if (__ballot(fl != 0) != 0) {                        // flagged codewords: their syndromes
-            static_for<0, C::NQ>([&](auto qc) {
-                constexpr int qd = decltype(qc)::value;
-                transpose8(Qs[qd]);
-                if (a.ws_pitch == 0) {
-#pragma unroll
-                    for (int jj = 0; jj < 4; ++jj)
-                        if (C::SYN[W][qd][jj] >= 0)
-                            pt::store_dword(rws, tile * (uint32_t)kSynTile + 256u * C::SYN[W][qd][jj] + 4u * pt::fresh(),
-                                            Qs[qd][jj]);
-                } else {                                     // a launch not starting a tile (shards)
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const uint32_t g = (uint32_t)a.ws_pitch + cw0 + k;
-                        const uint32_t row = (fl >> k & 1) ? (g >> 8) * (uint32_t)kSynTile + (g & 255u) : kOob;
-#pragma unroll
-                        for (int jj = 0; jj < 4; ++jj)
-                            if (C::SYN[W][qd][jj] >= 0)
-                                pt::store_byte(rws, row + 256u * C::SYN[W][qd][jj], Qs[qd][jj] >> (8 * k));
-                    }
-                }
-            });
-        }
-    }
-}
-
-template <class C, bool ENC, int W, bool SH, bool LO0>
-__device__ __forceinline__ void pq_run(const PsArgs &a, uint8_t *lds) {
-    const pw_rsrc_t rsrc = pw_rsrc(a.base, a.span);
-    const uint32_t lbuf = __builtin_amdgcn_readfirstlane(lds_addr(lds));
-    const pw_rsrc_t rout = pw_rsrc(reinterpret_cast<const uint8_t *>(a.result), ENC ? 0u : a.ncw * 4u);
-    const pw_rsrc_t rws = pw_rsrc(a.ws, ENC ? (uint32_t)(C::NR * a.ws_pitch)
-                                            : (uint32_t)((a.ws_pitch + a.ncw + 255) / 256 * kSynTile));
-    auto tile_range = [&](uint32_t t, uint32_t &bytes) -> uint32_t {
-        if (!SH) {
-            bytes = a.stride * kTile;
-            return t * bytes;
-        }
-        int lo;
-        const uint32_t t0 = t * kTile, off = pt::row_at(a, t0, lo);
-        bytes = (t0 + kTile < a.ncw ? pt::row_at(a, t0 + kTile, lo) : a.span) - off;
-        return pt::sh_align(off, bytes);
-    };
-    uint32_t tile = blockIdx.x;
-    PQ_RT(0);
-    uint32_t tbytes, toff = tile < a.ntiles ? tile_range(tile, tbytes) : 0u;
-    if (tile < a.ntiles) issue_tile(lbuf, rsrc, toff, tbytes, W);
-    int pq_it = 0;
-    (void)pq_it;
-    for (; tile < a.ntiles; tile += gridDim.x, ++pq_it) {
-        PQ_STAMP(0);
-        int lo = a.lo;
-        asm volatile("" : "+s"(lo));
-        uint32_t nbytes = 0;
-        const uint32_t noff = tile + gridDim.x < a.ntiles ? tile_range(tile + gridDim.x, nbytes) : kOob;
-        uint32_t V[C::NI][8];                                // set by the wave's first block
-        pt::wait_vm<0>();                                    // the tile landed (and the stores went)
-        if constexpr (SH) {                                  // row table: wave W writes rows 64W ..
-            const uint32_t r = 64u * (uint32_t)W + pt::fresh(), k = tile * kTile + r;
-            uint32_t e = kGuard;
-            if (k < a.ncw) {
-                int rlo;
-                const uint32_t at = pt::row_at(a, k, rlo);
-                e = (kGuard + at - toff - (uint32_t)rlo) | ((uint32_t)rlo << 24);
-            }
-            asm volatile("ds_write_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" :: "v"(lbuf + kTab + 4u * r), "v"(e) : "memory");
-        }
-        pt::barrier();
-        if (toff + tbytes >= a.span) {                       // last tile: the span's final bytes
-            if (W == 0) {
-                const uint32_t off = a.span - 64u + pt::fresh();
-                uint32_t v;
-                asm volatile("buffer_load_ubyte %0, %1, %2, 0 offen\n\ts_waitcnt vmcnt(0)"
-                             : "=&v"(v) : "v"(off), "s"(rsrc) : "memory");
-                if (off >= toff && off < a.span)
-                    asm volatile("ds_write_b8 %0, %1\n\ts_waitcnt lgkmcnt(0)"
-                                 :: "v"(lbuf + kGuard + (off - toff)), "v"(v) : "memory");
-            }
-            pt::barrier();
-        }
-        int tlo = lo;                                        // shard batches: pad of the tile's rows
-        if constexpr (SH) {
-            const uint32_t t0 = tile * kTile, kt = (t0 / a.srows) * a.srows + a.srows - 1;
-            if (kt < t0 + kTile && kt < a.ncw) tlo = a.stail_lo;
-        }
-        PQ_STAMP(1);
-        // the main loop outranks the other workgroup's waves on the SIMD (their exchange, DMA and
-        // fold): r04j C2 1203 vs 1169 GB/s; r06c: tails over main loops 1503, equal priority 1430,
-        // main loops over tails 1558 GB/s (profiles/r06/r06c_priority_ab.txt)
-        asm volatile("s_setprio 1");
-        pq_pass<C, ENC, W, SH, LO0>(V, lbuf, a.stride, lo, tlo);
-        asm volatile("s_setprio 0");
-        PQ_STAMP(2);
-        pt::barrier();                                       // the image is consumed
-        PQ_STAMP(3);
-        wave_tail<C, ENC, W>(V, a, lbuf, tile, noff, nbytes, rsrc, rout, rws, pq_it);
-        PQ_STAMP(6);
-        toff = noff;
-        tbytes = nbytes;
-    }
-    pt::wait_vm<0>();                                        // no DMA may land after the exit
-    PQ_RT(1);
-}
+};
 
 template <class C, bool ENC, bool SH, bool LO0>
 __global__ void __attribute__((amdgpu_flat_work_group_size(kThreads, kThreads), amdgpu_waves_per_eu(2)))
@@ -1063,10 +836,10 @@ k_pq_lin(PsArgs a) {
     __shared__ __attribute__((aligned(16))) uint8_t lds[kLds];
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     switch (w) {
-    case 0: pq_run<C, ENC, 0, SH, LO0>(a, lds); break;
-    case 1: pq_run<C, ENC, 1, SH, LO0>(a, lds); break;
-    case 2: pq_run<C, ENC, 2, SH, LO0>(a, lds); break;
-    default: pq_run<C, ENC, 3, SH, LO0>(a, lds); break;
+    case 0: tile_run<Tile, C, ENC, 0, SH, LO0>(a, lds); break;
+    case 1: tile_run<Tile, C, ENC, 1, SH, LO0>(a, lds); break;
+    case 2: tile_run<Tile, C, ENC, 2, SH, LO0>(a, lds); break;
+    default: tile_run<Tile, C, ENC, 3, SH, LO0>(a, lds); break;
     }
 }
 
@@ -1139,26 +912,26 @@ __global__ void __launch_bounds__(512) k_ps_parity8(const uint8_t *ws, size_t ws
     // wave w loads syndromes w + 8c (chunk c) -- every load in flight at once -- and makes chunk
     // c's planes visible when the passes reach it, so the map runs while later chunks arrive
     constexpr int NCH = (NR + 7) / 8;
-    pt::u32x4 v[NCH][2];
+    u32x4 v[NCH][2];
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {                            // plain loads: the compiler counts
         const int i = wave + 8 * c < NR ? wave + 8 * c : 0;   // them (past NR: a dummy row 0)
-        v[c][0] = *reinterpret_cast<const pt::u32x4 *>(src + i * ws_pitch);
-        v[c][1] = *reinterpret_cast<const pt::u32x4 *>(src + i * ws_pitch + 16);
+        v[c][0] = *reinterpret_cast<const u32x4 *>(src + i * ws_pitch);
+        v[c][1] = *reinterpret_cast<const u32x4 *>(src + i * ws_pitch + 16);
         __builtin_amdgcn_sched_barrier(0);                     // issue order = chunk order
     }
     auto ready = [&](auto cc) {
         constexpr int c = decltype(cc)::value;
         const int i = wave + 8 * c;
-        const pt::u32x4 a0 = v[c][0], a1 = v[c][1];
+        const u32x4 a0 = v[c][0], a1 = v[c][1];
         if (i < NR) {
             uint32_t D[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
             transpose8(D);                                     // D[q] bit 8k + m: cw 4m + k
 #pragma unroll
             for (int qq = 0; qq < 8; ++qq) lds[(8 * i + qq) * 64 + lane] = D[qq];
         }
-        pt::wait_lgkm();                                       // raw barrier: later chunks' loads stay in flight
-        pt::barrier();
+        wait_lgkm();                                           // raw barrier: later chunks' loads stay in flight
+        barrier();
     };
     ready(std::integral_constant<int, 0>{});
     PAR_STAMP(1);
@@ -1212,7 +985,7 @@ __global__ void __launch_bounds__(512) k_ps_parity8(const uint8_t *ws, size_t ws
             if constexpr (PB == 16) {
                 const uint2 lo = *reinterpret_cast<const uint2 *>(s8);      // the stage is 8-aligned
                 const uint2 hi = *reinterpret_cast<const uint2 *>(s8 + 8);
-                const pt::u32x4 v = {lo.x, lo.y, hi.x, hi.y};
+                const u32x4 v = {lo.x, lo.y, hi.x, hi.y};
                 __builtin_memcpy(dst + PB * sub, &v, 16);
             } else if constexpr (PB % 8 == 0) {
 #pragma unroll
@@ -1271,42 +1044,50 @@ unsigned syn_grid(const DevCodec &d, uint32_t ntiles) {
 
 } // namespace
 
-// Codecs with the 4-wave tile kernel (PQ_<codec>; codegen PQ_CODECS) use it for both directions
-// (r04f: C2 1161 vs 1062 GB/s on k_pt_lin); the others, and variant builds with -DEZRS_NO_PQ (A/B
-// timing, tools/build_variant.sh), run the 8-wave k_pt_lin.
-template <class PS> struct PqFor { using type = void; };
-#define EZRS_PQ_FOR(C) template <> struct PqFor<ps::PS_##C> { using type = ps::PQ_##C; };
-EZRS_PQ_CODEC_LIST(EZRS_PQ_FOR)
-#undef EZRS_PQ_FOR
+// Every codec runs exactly one tile kernel, for both directions: the 4-wave k_pq_lin for the codecs
+// of codegen's PQ_CODECS (r04f: C2 1161 vs 1062 GB/s on k_pt_lin), the 8-wave k_pt_lin for the
+// others.  Only that one is instantiated (the generated table still holds PT_<codec> for every
+// codec), so a variant build cannot A/B the two tile kernels on one codec; that takes a change of
+// PQ_CODECS and a regenerated table.
+template <class PS> struct IsPq : std::false_type {};
+template <class PS, bool PQ = IsPq<PS>::value> struct TileFor;
+#define EZRS_TILE_PQ(C)                                                                           \
+    template <> struct IsPq<ps::PS_##C> : std::true_type {};                                      \
+    template <> struct TileFor<ps::PS_##C, true> {                                                \
+        template <bool ENC, bool SH, bool LO0>                                                    \
+        static void launch(const ps::PsArgs &p, unsigned grid, hipStream_t s) {                   \
+            hipLaunchKernelGGL((ps::pq::k_pq_lin<ps::PQ_##C, ENC, SH, LO0>), dim3(grid),          \
+                               dim3(ps::pq::kThreads), 0, s, p);                                  \
+        }                                                                                         \
+    };
+#ifndef EZRS_PQ_ONLY
+#define EZRS_TILE_PT(C)                                                                           \
+    template <> struct TileFor<ps::PS_##C, false> {                                               \
+        template <bool ENC, bool SH, bool LO0>                                                    \
+        static void launch(const ps::PsArgs &p, unsigned grid, hipStream_t s) {                   \
+            hipLaunchKernelGGL((ps::pt::k_pt_lin<ps::PT_##C, ENC, SH, LO0>), dim3(grid),          \
+                               dim3(ps::pt::kThreads), 0, s, p);                                  \
+        }                                                                                         \
+    };
+#else                                                         // (ISA inspection builds: tools/pq_isa.sh)
+#define EZRS_TILE_PT(C)                                                                           \
+    template <> struct TileFor<ps::PS_##C, false> {                                               \
+        template <bool ENC, bool SH, bool LO0> static void launch(const ps::PsArgs &, unsigned, hipStream_t) {} \
+    };
+#endif
+EZRS_PQ_CODEC_LIST(EZRS_TILE_PQ)
+EZRS_PS_CODEC_LIST(EZRS_TILE_PT)                              // used by the codecs that are not PQ
+#undef EZRS_TILE_PQ
+#undef EZRS_TILE_PT
 
-template <class PS, class PT, bool ENC>
+template <class PS, bool ENC>
 void launch_tile(const ps::PsArgs &p, bool shard, unsigned grid, hipStream_t s) {
-    using PQ = typename PqFor<PS>::type;
-#ifndef EZRS_NO_PQ
-    if constexpr (!std::is_void<PQ>::value) {
-        const bool lo0 = p.lo == 0;                          // full-length rows: no pad masks
-        if (shard && lo0)
-            hipLaunchKernelGGL((ps::pq::k_pq_lin<PQ, ENC, true, true>), dim3(grid), dim3(ps::pq::kThreads), 0, s, p);
-        else if (shard)
-            hipLaunchKernelGGL((ps::pq::k_pq_lin<PQ, ENC, true, false>), dim3(grid), dim3(ps::pq::kThreads), 0, s, p);
-        else if (lo0)
-            hipLaunchKernelGGL((ps::pq::k_pq_lin<PQ, ENC, false, true>), dim3(grid), dim3(ps::pq::kThreads), 0, s, p);
-        else
-            hipLaunchKernelGGL((ps::pq::k_pq_lin<PQ, ENC, false, false>), dim3(grid), dim3(ps::pq::kThreads), 0, s, p);
-        return;
-    }
-#endif
-#ifndef EZRS_PQ_ONLY                                          // (ISA inspection builds: tools/pq_isa.sh)
+    using T = TileFor<PS>;
     const bool lo0 = p.lo == 0;                              // full-length rows: no pad masks
-    if (shard && lo0)
-        hipLaunchKernelGGL((ps::pt::k_pt_lin<PT, ENC, true, true>), dim3(grid), dim3(ps::pt::kThreads), 0, s, p);
-    else if (shard)
-        hipLaunchKernelGGL((ps::pt::k_pt_lin<PT, ENC, true, false>), dim3(grid), dim3(ps::pt::kThreads), 0, s, p);
-    else if (lo0)
-        hipLaunchKernelGGL((ps::pt::k_pt_lin<PT, ENC, false, true>), dim3(grid), dim3(ps::pt::kThreads), 0, s, p);
-    else
-        hipLaunchKernelGGL((ps::pt::k_pt_lin<PT, ENC, false, false>), dim3(grid), dim3(ps::pt::kThreads), 0, s, p);
-#endif
+    if (shard && lo0) T::template launch<ENC, true, true>(p, grid, s);
+    else if (shard) T::template launch<ENC, true, false>(p, grid, s);
+    else if (lo0) T::template launch<ENC, false, true>(p, grid, s);
+    else T::template launch<ENC, false, false>(p, grid, s);
 }
 
 int planeslice_codec_id(const DevCodec &d) {
@@ -1317,18 +1098,6 @@ int planeslice_codec_id(const DevCodec &d) {
     EZRS_PS_CODEC_LIST(EZRS_PS_MATCH)
 #undef EZRS_PS_MATCH
     return found;
-}
-
-// Timing experiments only: EZRS_PT_ABLATE disables phases of the tile kernel (PsArgs::ablate).  Read
-// only by variant builds compiled with -DEZRS_PT_ABLATE_ENV (tools/build_variant.sh); the release
-// library never looks at the environment here, so a stray variable cannot switch correction off.
-static int pt_ablate() {
-#ifdef EZRS_PT_ABLATE_ENV
-    const char *e = getenv("EZRS_PT_ABLATE");
-    return e ? atoi(e) : 0;
-#else
-    return 0;
-#endif
 }
 
 // Workspace: decode tiled syndromes (kSynTile); encode [NR][ws_pitch] syndromes, ws_pitch = ncw
@@ -1402,13 +1171,12 @@ hipError_t launch_ps_encode(int id, const DevCodec &d, const EncodeArgs &a, void
         uint8_t *par = a.sh.rows ? const_cast<uint8_t *>(p.base) : static_cast<uint8_t *>(a.parity) + k0 * a.parity_stride;
         p.ws = static_cast<uint8_t *>(ws);
         p.ws_pitch = ps_pitch(n);
-        p.ablate = pt_ablate();
         const unsigned grid = syn_grid(d, p.ntiles);
         int k = 0;
 #define EZRS_PS_ENC(C)                                                                            \
         if (k++ == id) {                                                                          \
             const unsigned pgrid = (unsigned)((n + ps::kParCw - 1) / ps::kParCw);                 \
-            launch_tile<ps::PS_##C, ps::PT_##C, true>(p, a.sh.rows != 0, grid, s);                \
+            launch_tile<ps::PS_##C, true>(p, a.sh.rows != 0, grid, s);                            \
             launch_parity<ps::PS_##C>(d, static_cast<const uint8_t *>(ws), p.ws_pitch, par,     \
                                       a.parity_stride, n, a.sh, a.len, pgrid, s);                 \
         }
@@ -1443,13 +1211,12 @@ hipError_t launch_ps_syndromes(int id, const DevCodec &d, const DecodeArgs &a, u
         p.result = a.result + k0;
         p.ws = syn_ws + k0 / 256 * kSynTile;                  // tiled layout, global codeword index
         p.ws_pitch = k0 % 256;
-        p.ablate = pt_ablate();
         p.flag = a.flag_word;
         p.gen = a.flag_gen;
         const unsigned grid = syn_grid(d, p.ntiles);
         int k = 0;
 #define EZRS_PS_SYN(C)                                                                            \
-        if (k++ == id) launch_tile<ps::PS_##C, ps::PT_##C, false>(p, a.sh.rows != 0, grid, s);
+        if (k++ == id) launch_tile<ps::PS_##C, false>(p, a.sh.rows != 0, grid, s);
         EZRS_PS_CODEC_LIST(EZRS_PS_SYN)
 #undef EZRS_PS_SYN
         hipError_t e = hipGetLastError();

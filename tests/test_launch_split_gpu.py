@@ -32,7 +32,9 @@ def _corrupt(rng, cw, L, nr, ncw):
     return eras, neras
 
 
-@pytest.mark.parametrize("k,L,rows", [(223, 223, 1000), (223, 16, 300), (247, 40, 2049), (251, 200, 5)])
+@pytest.mark.parametrize("k,L,rows", [(223, 223, 1000), (223, 16, 300), (247, 40, 2049), (251, 200, 5),
+                                      # the 8-wave tile kernel, full-length rows, a partial last tile
+                                      (248, 248, 300), (253, 253, 257)])
 def test_plain_batch_split_vs_oracle(torch, k, L, rows):
     import ezrs
     c = ezrs.Codec.rs(255, k)

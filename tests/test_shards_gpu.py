@@ -67,6 +67,10 @@ CASES = [
     (255, 223, 1000, 200, 300, 0),        # chunks shorter than the load: every row shortened
     (255, 239, 4096, 239, 90, 0),
     (255, 251, 2000, 251, 150, 1),
+    # the 8-wave tile kernel's codecs (row table of 32 rows per wave)
+    (255, 248, 1024, 248, 300, 0),        # shortened last row, more than one tile
+    (255, 248, 600, 200, 130, 5),         # every row shortened, padded pitch
+    (255, 252, 252, 252, 260, 0),         # one full codeword per shard, a tile boundary in the batch
 ]
 
 
