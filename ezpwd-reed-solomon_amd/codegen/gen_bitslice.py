@@ -28,7 +28,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
-from gf8 import Codec8  # noqa: E402
+from gf8 import Codec8, emit_combos  # noqa: E402
 
 # (name, poly, fcr, prim, nroots, dual) -- the codecs with a bit-sliced fast path
 CODECS = [
@@ -68,20 +68,6 @@ def fmt(arr, depth=0):
     if isinstance(arr, list):
         return "{" + ",".join(fmt(a, depth + 1) for a in arr) + "}"
     return str(arr)
-
-
-def emit_combos(out, name, srcs, ind):
-    a = srcs
-    out.append(f"{ind}const uint32_t {name}1 = {a[0]}, {name}2 = {a[1]}, {name}4 = {a[2]}, {name}8 = {a[3]};")
-    out.append(f"{ind}const uint32_t {name}3 = {name}1 ^ {name}2, {name}5 = {name}1 ^ {name}4, "
-               f"{name}6 = {name}2 ^ {name}4, {name}9 = {name}1 ^ {name}8, {name}10 = {name}2 ^ {name}8, "
-               f"{name}12 = {name}4 ^ {name}8;")
-    out.append(f"{ind}const uint32_t {name}7 = {name}3 ^ {name}4, {name}11 = {name}3 ^ {name}8, "
-               f"{name}13 = {name}5 ^ {name}8, {name}14 = {name}6 ^ {name}8;")
-    out.append(f"{ind}const uint32_t {name}15 = {name}7 ^ {name}8;")
-    out.append(f"{ind}(void){name}1; (void){name}2; (void){name}3; (void){name}4; (void){name}5; "
-               f"(void){name}6; (void){name}7; (void){name}8; (void){name}9; (void){name}10; "
-               f"(void){name}11; (void){name}12; (void){name}13; (void){name}14; (void){name}15;")
 
 
 def upd(dst, acc, m, lo="l", hi="h"):

@@ -34,7 +34,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
-from gf8 import GF8, gf_mat_inv, lin_rows  # noqa: E402
+from gf8 import GF8, emit_combos, gf_mat_inv, lin_rows  # noqa: E402
 
 N = 255
 
@@ -60,7 +60,12 @@ CODECS = [
 
 
 def fmt_list(xs):
-    return "{" + ", ".join(str(x) for x in xs) + "}"
+    """A C++ brace initialiser of the (nested) list xs."""
+    return "{" + ", ".join(fmt_list(x) if isinstance(x, (list, tuple)) else str(x) for x in xs) + "}"
+
+
+def pad(xs, n, v=-1):
+    return list(xs) + [v] * (n - len(xs))
 
 
 class PsCodec:
@@ -120,20 +125,6 @@ def xor_chain(dst, terms, ind):
         else:
             acc, rest = f"({acc} ^ {rest[0]})", rest[1:]
     return [f"{ind}{dst} = {acc};"]
-
-
-def emit_combos(out, name, srcs, ind):
-    a = srcs
-    out.append(f"{ind}const uint32_t {name}1 = {a[0]}, {name}2 = {a[1]}, {name}4 = {a[2]}, {name}8 = {a[3]};")
-    out.append(f"{ind}const uint32_t {name}3 = {name}1 ^ {name}2, {name}5 = {name}1 ^ {name}4, "
-               f"{name}6 = {name}2 ^ {name}4, {name}9 = {name}1 ^ {name}8, {name}10 = {name}2 ^ {name}8, "
-               f"{name}12 = {name}4 ^ {name}8;")
-    out.append(f"{ind}const uint32_t {name}7 = {name}3 ^ {name}4, {name}11 = {name}3 ^ {name}8, "
-               f"{name}13 = {name}5 ^ {name}8, {name}14 = {name}6 ^ {name}8;")
-    out.append(f"{ind}const uint32_t {name}15 = {name}7 ^ {name}8;")
-    out.append(f"{ind}(void){name}1; (void){name}2; (void){name}3; (void){name}4; (void){name}5; "
-               f"(void){name}6; (void){name}7; (void){name}8; (void){name}9; (void){name}10; "
-               f"(void){name}11; (void){name}12; (void){name}13; (void){name}14; (void){name}15;")
 
 
 def mat_apply(out, dst, src, rows, ind, extra=None):
@@ -497,74 +488,40 @@ class PtRole:
             self.pieces[w] = (h0, h1)
 
 
-def gen_pt(c: PsCodec):
-    """Tile-kernel tables and straight-line code, PT_<codec>: syndromes by coset leaders, the
-    leaders split into GN groups, the positions into QN quarters.  Wave (g, q) reads pieces
-    q, q + QN, q + 2 QN, ... and runs each piece's own networks on them (block index = the piece's
-    absolute 8-position block).  Encode evaluates the same syndromes over the data positions (the
-    kernel masks positions >= K) for k_ps_parity8."""
-    out = []
-    R = PtRole(c, False)
-    st = f"PT_{c.name}"
-    W = PT_WAVES
-    mp = max(max(len(R.pieces[w][0]) + len(R.pieces[w][1]) for w in range(W)), 1)
+def emit_tile(st, c: PsCodec, R: PtRole, *, lead, mid, split, partner, block_decl, blocks):
+    """struct <st> (PT_<codec> or PQ_<codec>): what the two tile kernels' tables share.  From the
+    plan R come the exchange (XR, XS, XV), ownership (OWN) and syndrome (SYN) tables, the per-wave
+    fold epilogues and their dispatcher.  The kernel gives its own constants (lead, mid: "NAME =
+    value"), its position-split tables (split), the shift unit of the exchange partner, block<>'s
+    declaration and its specialisations blocks = [(block<> arguments before F, weight functions,
+    8-position block, first)]."""
+    W, X = R.nwaves, R.xcap
     nsub = max(len(R.subs), 1)
-
-    def pad(xs, n, v=-1):
-        return list(xs) + [v] * (n - len(xs))
-    X = PT_XCAP
-    xs = [[pad(R.waves[w]["plan"][r][0][X * ch:X * ch + X], X) for (r, ch) in R.subs] or [[-1] * X]
-          for w in range(W)]
-    xv = [[pad(R.waves[w]["plan"][r][1][X * ch:X * ch + X], X) for (r, ch) in R.subs] or [[-1] * X]
-          for w in range(W)]
+    xs, xv = ([[pad(R.waves[w]["plan"][r][d][X * ch:X * ch + X], X) for (r, ch) in R.subs] or [[-1] * X]
+               for w in range(W)] for d in (0, 1))
     syn = [[[R.waves[w]["seq"][4 * qd + j][1] if 4 * qd + j < len(R.waves[w]["seq"]) else -1
              for j in range(4)] for qd in range(R.nq)] for w in range(W)]
-    for w in range(W):                                  # pieces of wave (g, q) = quarter 0's + q
-        q = R.waves[w]["q"]
-        p0 = R.pieces[R.waves[w]["g"]][0] + R.pieces[R.waves[w]["g"]][1]
-        mine = R.pieces[w][0] + R.pieces[w][1]
-        assert mine == [p + q for p in p0][:len(mine)], (w, mine, p0)
-    hdr = [f"struct {st} {{",
+    out = [f"struct {st} {{",
            f"    static constexpr unsigned POLY = {c.poly:#x}, FCR = {c.fcr}, PRIM = {c.prim}, NR = {c.nr};",
-           f"    static constexpr int GN = {R.gn}, QN = {R.qn}, NI = {R.ni}, NOWN = {R.nown}, NQ = {R.nq};",
-           f"    static constexpr int NSUB = {len(R.subs)}, MP = {mp}, XCAP = {X};",
-           "    // pieces (16 positions) of wave W: NP0 in half 0, then NP1 in half 1 (decode: 255",
-           "    // positions; encode stops at the data positions)",
-           f"    static constexpr int NP0[{W}] = {fmt_list([len(R.pieces[w][0]) for w in range(W)])};",
-           f"    static constexpr int NP1[{W}] = {fmt_list([len(R.pieces[w][1]) for w in range(W)])};",
-           f"    static constexpr int PIECE[{W}][{mp}] = " + "{" + ", ".join(
-               fmt_list(pad(R.pieces[w][0] + R.pieces[w][1], mp)) for w in range(W)) + "};",
+           "    static constexpr int " + ", ".join(lead + [f"NI = {R.ni}", f"NOWN = {R.nown}", f"NQ = {R.nq}"]) + ";",
+           "    static constexpr int " + ", ".join([f"NSUB = {len(R.subs)}"] + mid + [f"XCAP = {X}"]) + ";",
+           *split,
            "    // exchange sub-round s (round XR[s]): wave W sends item slots XS[W][s], adds the",
-           "    // partner's words into slots XV[W][s] (partner = W ^ (GN << XR[s]))",
+           f"    // partner's words into slots XV[W][s] (partner = W ^ ({partner} << XR[s]))",
            f"    static constexpr int XR[{nsub}] = {fmt_list([r for r, _ in R.subs] or [0])};",
-           f"    static constexpr int XS[{W}][{nsub}][{X}] = " + "{" + ", ".join(
-               "{" + ", ".join(fmt_list(x) for x in xs[w]) + "}" for w in range(W)) + "};",
-           f"    static constexpr int XV[{W}][{nsub}][{X}] = " + "{" + ", ".join(
-               "{" + ", ".join(fmt_list(x) for x in xv[w]) + "}" for w in range(W)) + "};",
+           f"    static constexpr int XS[{W}][{nsub}][{X}] = {fmt_list(xs)};",
+           f"    static constexpr int XV[{W}][{nsub}][{X}] = {fmt_list(xv)};",
            "    // item slots whose totals wave W folds (T[i] <-> slot OWN[W][i])",
-           f"    static constexpr int OWN[{W}][{R.nown}] = " + "{" + ", ".join(
-               fmt_list(pad(R.waves[w]["own"], R.nown)) for w in range(W)) + "};",
+           f"    static constexpr int OWN[{W}][{R.nown}] = {fmt_list([pad(R.waves[w]['own'], R.nown) for w in range(W)])};",
            "    // syndrome index of quad slot (W, quad, j), -1 = none",
-           f"    static constexpr int SYN[{W}][{R.nq}][4] = " + "{" + ", ".join(
-               "{" + ", ".join(fmt_list(q) for q in syn[w]) + "}" for w in range(W)) + "};",
-           "    // positions 8B..8B+7 (words X) into group G's state (B: the absolute 8-position block;",
-           "    // F: the wave's first block, which sets the state instead of accumulating into it)",
-           "    template <int G, int B, bool F> static __device__ void block(uint32_t (&V)[NI][8], const uint32_t (&X)[8]);",
+           f"    static constexpr int SYN[{W}][{R.nq}][4] = {fmt_list(syn)};",
+           *block_decl,
            "    template <int W, class F, class H> static __device__ void epilogue(const uint32_t (&T)[NOWN][8], F &&emit, "
            "H &&hook);",
            "};"]
-    out += hdr
-    gf = c.gf
-    for g, gitems in enumerate(R.groups):
-        ws = [R.wfun[i] for i in gitems]
-        # every wave of group g runs its own pieces' networks (block index = absolute 8-position
-        # block), so no quarter needs a fix-up
-        pall = sorted(set(p for w in range(W) if R.waves[w]["g"] == g for p in R.pieces[w][0] + R.pieces[w][1]))
-        for pc in pall:
-            for B in (2 * pc, 2 * pc + 1):
-                for F in ((True, False) if B == 2 * pc else (False,)):
-                    emit_weight_block(out, f"template <> __device__ __forceinline__ void {st}::block<{g}, {B}, {str(F).lower()}>("
-                                      "uint32_t (&V)[NI][8], const uint32_t (&X)[8])", ws, B, first=F, opaque=True)
+    for args, ws, B, F in blocks:
+        emit_weight_block(out, f"template <> __device__ __forceinline__ void {st}::block<{args}, {str(F).lower()}>("
+                          "uint32_t (&V)[NI][8], const uint32_t (&X)[8])", ws, B, first=F, opaque=True)
     for w in range(W):
         emit_fold_epilogue(out, c.gf, f"{st}_epi{w}", "T", f"{st}::NOWN", R.waves[w]["seq"])
     out.append(f"template <int W, class F, class H> __device__ __forceinline__ void {st}::epilogue("
@@ -572,6 +529,43 @@ def gen_pt(c: PsCodec):
     out.append("    " + " else ".join(f"if constexpr (W == {w}) {st}_epi{w}(T, emit, hook);" for w in range(W)))
     out.append("}")
     return "\n".join(out)
+
+
+def gen_pt(c: PsCodec):
+    """Tile-kernel tables and straight-line code, PT_<codec>: syndromes by coset leaders, the
+    leaders split into GN groups, the positions into QN quarters.  Wave (g, q) reads pieces
+    q, q + QN, q + 2 QN, ... and runs each piece's own networks on them (block index = the piece's
+    absolute 8-position block).  Encode evaluates the same syndromes over the data positions (the
+    kernel masks positions >= K) for k_ps_parity8."""
+    R = PtRole(c, False)
+    W = PT_WAVES
+    mp = max(max(len(R.pieces[w][0]) + len(R.pieces[w][1]) for w in range(W)), 1)
+    for w in range(W):                               # pieces of wave (g, q) = quarter 0's + q
+        q = R.waves[w]["q"]
+        p0 = R.pieces[R.waves[w]["g"]][0] + R.pieces[R.waves[w]["g"]][1]
+        mine = R.pieces[w][0] + R.pieces[w][1]
+        assert mine == [p + q for p in p0][:len(mine)], (w, mine, p0)
+    split = ["    // pieces (16 positions) of wave W: NP0 in half 0, then NP1 in half 1 (decode: 255",
+             "    // positions; encode stops at the data positions)",
+             f"    static constexpr int NP0[{W}] = {fmt_list([len(R.pieces[w][0]) for w in range(W)])};",
+             f"    static constexpr int NP1[{W}] = {fmt_list([len(R.pieces[w][1]) for w in range(W)])};",
+             f"    static constexpr int PIECE[{W}][{mp}] = "
+             f"{fmt_list([pad(R.pieces[w][0] + R.pieces[w][1], mp) for w in range(W)])};"]
+    block_decl = [
+        "    // positions 8B..8B+7 (words X) into group G's state (B: the absolute 8-position block;",
+        "    // F: the wave's first block, which sets the state instead of accumulating into it)",
+        "    template <int G, int B, bool F> static __device__ void block(uint32_t (&V)[NI][8], const uint32_t (&X)[8]);"]
+    blocks = []                                         # (block<> arguments, weights, B, first)
+    for g, gitems in enumerate(R.groups):
+        ws = [R.wfun[i] for i in gitems]
+        # every wave of group g runs its own pieces' networks (block index = absolute 8-position
+        # block), so no quarter needs a fix-up
+        pall = sorted(set(p for w in range(W) if R.waves[w]["g"] == g for p in R.pieces[w][0] + R.pieces[w][1]))
+        for pc in pall:
+            for B in (2 * pc, 2 * pc + 1):
+                blocks += [(f"{g}, {B}", ws, B, F) for F in ((True, False) if B == 2 * pc else (False,))]
+    return emit_tile(f"PT_{c.name}", c, R, lead=[f"GN = {R.gn}", f"QN = {R.qn}"], mid=[f"MP = {mp}"],
+                     split=split, partner="GN", block_decl=block_decl, blocks=blocks)
 
 
 # ---- 4-wave tile kernel (k_pq): each wave evaluates ALL leaders over its own run of positions ------
@@ -587,21 +581,8 @@ def gen_pq(c: PsCodec):
     are done once per position); a two-round recursive-halving exchange then leaves every wave the
     totals of the leaders whose syndromes (two quads) it folds.  Encode runs the same networks over
     the data positions (the kernel masks positions >= K) for k_ps_parity8."""
-    out = []
     R = PtRole(c, False, waves=PQ_WAVES, gn=1, xcap=PQ_XCAP)
-    st = f"PQ_{c.name}"
     W = PQ_WAVES
-    X = PQ_XCAP
-    nsub = max(len(R.subs), 1)
-
-    def pad(xs, n, v=-1):
-        return list(xs) + [v] * (n - len(xs))
-    xs = [[pad(R.waves[w]["plan"][r][0][X * ch:X * ch + X], X) for (r, ch) in R.subs] or [[-1] * X]
-          for w in range(W)]
-    xv = [[pad(R.waves[w]["plan"][r][1][X * ch:X * ch + X], X) for (r, ch) in R.subs] or [[-1] * X]
-          for w in range(W)]
-    syn = [[[R.waves[w]["seq"][4 * qd + j][1] if 4 * qd + j < len(R.waves[w]["seq"]) else -1
-             for j in range(4)] for qd in range(R.nq)] for w in range(W)]
     # 8-position blocks per direction, split into W contiguous runs (decode: all N positions;
     # encode: the data positions)
     runs = []
@@ -609,45 +590,17 @@ def gen_pq(c: PsCodec):
         nb = -(-hi // 8)
         cut = [round(nb * w / W) for w in range(W + 1)]
         runs.append((nb, cut))
-    hdr = [f"struct {st} {{",
-           f"    static constexpr unsigned POLY = {c.poly:#x}, FCR = {c.fcr}, PRIM = {c.prim}, NR = {c.nr};",
-           f"    static constexpr int NI = {R.ni}, NOWN = {R.nown}, NQ = {R.nq};",
-           f"    static constexpr int NSUB = {len(R.subs)}, XCAP = {X};",
-           "    // 8-position blocks of wave W: [B0[E][W], B0[E][W + 1]) (E = 0 decode, 1 encode)",
-           f"    static constexpr int NB[2] = {{{runs[0][0]}, {runs[1][0]}}};",
-           f"    static constexpr int B0[2][{W + 1}] = {{{fmt_list(runs[0][1])}, {fmt_list(runs[1][1])}}};",
-           "    // exchange sub-round s (round XR[s]): wave W sends item slots XS[W][s], adds the",
-           "    // partner's words into slots XV[W][s] (partner = W ^ (1 << XR[s]))",
-           f"    static constexpr int XR[{nsub}] = {fmt_list([r for r, _ in R.subs] or [0])};",
-           f"    static constexpr int XS[{W}][{nsub}][{X}] = " + "{" + ", ".join(
-               "{" + ", ".join(fmt_list(x) for x in xs[w]) + "}" for w in range(W)) + "};",
-           f"    static constexpr int XV[{W}][{nsub}][{X}] = " + "{" + ", ".join(
-               "{" + ", ".join(fmt_list(x) for x in xv[w]) + "}" for w in range(W)) + "};",
-           "    // item slots whose totals wave W folds (T[i] <-> slot OWN[W][i])",
-           f"    static constexpr int OWN[{W}][{R.nown}] = " + "{" + ", ".join(
-               fmt_list(pad(R.waves[w]["own"], R.nown)) for w in range(W)) + "};",
-           "    // syndrome index of quad slot (W, quad, j), -1 = none",
-           f"    static constexpr int SYN[{W}][{R.nq}][4] = " + "{" + ", ".join(
-               "{" + ", ".join(fmt_list(q) for q in syn[w]) + "}" for w in range(W)) + "};",
-           "    // positions 8B..8B+7 (words X) into every leader's state",
-           "    // F: the wave's first block (sets the state instead of accumulating into it)",
-           "    template <int B, bool F> static __device__ void block(uint32_t (&V)[NI][8], const uint32_t (&X)[8]);",
-           "    template <int W, class F, class H> static __device__ void epilogue(const uint32_t (&T)[NOWN][8], F &&emit, "
-           "H &&hook);",
-           "};"]
-    out += hdr
+    split = ["    // 8-position blocks of wave W: [B0[E][W], B0[E][W + 1]) (E = 0 decode, 1 encode)",
+             f"    static constexpr int NB[2] = {fmt_list([nb for nb, _ in runs])};",
+             f"    static constexpr int B0[2][{W + 1}] = {fmt_list([cut for _, cut in runs])};"]
+    block_decl = [
+        "    // positions 8B..8B+7 (words X) into every leader's state",
+        "    // F: the wave's first block (sets the state instead of accumulating into it)",
+        "    template <int B, bool F> static __device__ void block(uint32_t (&V)[NI][8], const uint32_t (&X)[8]);"]
     ws = [R.wfun[i] for i in R.groups[0]]
-    for B in range(runs[0][0]):
-        for F in (True, False):
-            emit_weight_block(out, f"template <> __device__ __forceinline__ void {st}::block<{B}, {str(F).lower()}>("
-                              "uint32_t (&V)[NI][8], const uint32_t (&X)[8])", ws, B, first=F, opaque=True)
-    for w in range(W):
-        emit_fold_epilogue(out, c.gf, f"{st}_epi{w}", "T", f"{st}::NOWN", R.waves[w]["seq"])
-    out.append(f"template <int W, class F, class H> __device__ __forceinline__ void {st}::epilogue("
-               "const uint32_t (&T)[NOWN][8], F &&emit, H &&hook) {")
-    out.append("    " + " else ".join(f"if constexpr (W == {w}) {st}_epi{w}(T, emit, hook);" for w in range(W)))
-    out.append("}")
-    return "\n".join(out)
+    blocks = [(f"{B}", ws, B, F) for B in range(runs[0][0]) for F in (True, False)]
+    return emit_tile(f"PQ_{c.name}", c, R, lead=[], mid=[], split=split, partner="1",
+                     block_decl=block_decl, blocks=blocks)
 
 
 def main(dst=None):

@@ -1,4 +1,5 @@
-"""GF(2^8) helpers for the bit-sliced kernel generator (host-side, build time only).
+"""GF(2^8) helpers and the shared Four-Russians emitter of the kernel generators (host-side, build
+time only).
 
 Field, generator roots and dual-basis conventions follow c++/ezpwd/rs_base:537-635 (tables),
 1263-1285 (roots alpha^((fcr+i)*prim)) and 109-146 (CCSDS dual basis)."""
@@ -96,6 +97,22 @@ def gf_mat_inv(gf, A):
                 f = M[r][col]
                 M[r] = [a ^ gf.mul(f, b) for a, b in zip(M[r], M[col])]
     return [row[n:] for row in M]
+
+
+def emit_combos(out, name, srcs, ind):
+    """Four-Russians combinations: the 15 XORs <name>1 .. <name>15 of the four words srcs
+    (<name>m = XOR of srcs[t] over the bits t of m), as C++ lines appended to out."""
+    a = srcs
+    out.append(f"{ind}const uint32_t {name}1 = {a[0]}, {name}2 = {a[1]}, {name}4 = {a[2]}, {name}8 = {a[3]};")
+    out.append(f"{ind}const uint32_t {name}3 = {name}1 ^ {name}2, {name}5 = {name}1 ^ {name}4, "
+               f"{name}6 = {name}2 ^ {name}4, {name}9 = {name}1 ^ {name}8, {name}10 = {name}2 ^ {name}8, "
+               f"{name}12 = {name}4 ^ {name}8;")
+    out.append(f"{ind}const uint32_t {name}7 = {name}3 ^ {name}4, {name}11 = {name}3 ^ {name}8, "
+               f"{name}13 = {name}5 ^ {name}8, {name}14 = {name}6 ^ {name}8;")
+    out.append(f"{ind}const uint32_t {name}15 = {name}7 ^ {name}8;")
+    out.append(f"{ind}(void){name}1; (void){name}2; (void){name}3; (void){name}4; (void){name}5; "
+               f"(void){name}6; (void){name}7; (void){name}8; (void){name}9; (void){name}10; "
+               f"(void){name}11; (void){name}12; (void){name}13; (void){name}14; (void){name}15;")
 
 
 class Codec8:
