@@ -35,6 +35,7 @@
 #include "../../include/ezbch.h"
 #include "ezbch_ps_tile.hpp"
 #include "ezrs_internal.hpp"
+#include "ezrs_host.hpp"
 
 using ezrs::BpsArgs;
 using ezrs::bps_codec_id;
@@ -1309,31 +1310,12 @@ hipError_t launch_decode(const DevBch &b, BchArgs a, hipStream_t s) {
 }
 
 // ---- host --------------------------------------------------------------------------------------
+using ezrs::align_up;
+using ezrs::DeviceGuard;
+
 thread_local std::string g_err;
 
-int hip_fail(hipError_t e, const char *what) {
-    g_err = std::string(what) + ": " + hipGetErrorString(e);
-    if (e == hipErrorOutOfMemory) return -ENOMEM;
-    if (e == hipErrorNoDevice || e == hipErrorInvalidDevice) return -ENODEV;
-    return -EIO;
-}
-
-#define HIP_TRY(expr)                                          \
-    do {                                                       \
-        hipError_t e_ = (expr);                                \
-        if (e_ != hipSuccess) return hip_fail(e_, #expr);      \
-    } while (0)
-
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
+int hip_fail(hipError_t e, const char *what) { return ezrs::hip_fail(g_err, e, what); }
 
 // init_bch's default primitive polynomials, m = 5..15
 const unsigned kDefaultPoly[11] = {0x25, 0x43, 0x83, 0x11d, 0x211, 0x409,
@@ -1432,10 +1414,8 @@ struct ezbch_codec {
     uint16_t *d_tabs = nullptr;
     uint64_t *d_syn = nullptr;    // DevBch::syn_tab
     std::mutex mu;                // guards the host-pipeline buffers
-    void *d_stage = nullptr;
-    size_t stage_bytes = 0;
-    void *h_stage = nullptr;      // pinned host staging (gathers, compact ECC)
-    size_t hstage_bytes = 0;
+    ezrs::StageBufs<1> d_stage;
+    ezrs::StageBufs<1, hipHostMallocDefault> h_stage;   // pinned host staging (gathers, compact ECC)
     hipStream_t stream = nullptr;
 };
 
@@ -1520,42 +1500,44 @@ int create_impl(ezbch_codec **out, unsigned m, unsigned t, unsigned poly, int de
     return 0;
 }
 
-int check_args(const ezbch_codec *c, const uint8_t *data, size_t dstride, unsigned len,
-               const uint8_t *ecc, size_t estride, size_t ncw) {
-    if (!data || !ecc) return -EINVAL;
+// Row geometry of a batch.  ecc == NULL is the row form, legal where row_form is set: the ECC
+// follows the data in each row, and ecc / estride are resolved to it.  The stride rules hold for
+// ncw > 1 only.
+int check_rows(const ezbch_codec *c, const uint8_t *data, size_t dstride, unsigned len, uint8_t *&ecc,
+               size_t &estride, size_t ncw, bool row_form) {
+    if (!data || (!ecc && !row_form)) return -EINVAL;
+    if (!ecc) {
+        if (ncw > 1 && dstride < (size_t)len + c->h.ecc_bytes) return -EINVAL;
+        ecc = const_cast<uint8_t *>(data) + len;
+        estride = dstride;
+    }
     if (ncw > 1 && (estride < c->h.ecc_bytes || dstride < len)) return -EINVAL;
     return 0;
 }
 
-// Row form: the ECC follows the data in each row.
-int check_rows(const ezbch_codec *c, const uint8_t *rows, size_t stride, unsigned len, size_t ncw) {
-    if (!rows) return -EINVAL;
-    if (ncw > 1 && stride < (size_t)len + c->h.ecc_bytes) return -EINVAL;
-    return 0;
+// errloc rows hold up to t positions each.
+bool bad_errloc(const ezbch_codec *c, const uint32_t *errloc, size_t errloc_stride, size_t ncw) {
+    return errloc && ncw > 1 && errloc_stride < c->h.t;
+}
+
+// The kernels of one checked batch on the codec's device.
+int run(const ezbch_codec *c, const BchArgs &a, bool decode, void *stream) {
+    DeviceGuard g(c->device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipError_t e = decode ? launch_decode(c->dev, a, st) : launch_encode(c->dev, a, st);
+    return e == hipSuccess ? 0 : hip_fail(e, decode ? "BCH decode launch" : "BCH encode launch");
 }
 
 int ensure_hstage(ezbch_codec *c, size_t bytes) {
-    if (c->hstage_bytes >= bytes) return 0;
-    if (c->h_stage) (void)hipHostFree(c->h_stage);
-    c->h_stage = nullptr;
-    c->hstage_bytes = 0;
-    HIP_TRY(hipHostMalloc(&c->h_stage, bytes, hipHostMallocDefault));
-    c->hstage_bytes = bytes;
+    HIP_TRY(c->h_stage.ensure(bytes));
     return 0;
 }
 
 int ensure_stage(ezbch_codec *c, size_t bytes) {
     if (!c->stream) HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    if (c->stage_bytes >= bytes) return 0;
-    if (c->d_stage) (void)hipFree(c->d_stage);
-    c->d_stage = nullptr;
-    c->stage_bytes = 0;
-    HIP_TRY(hipMalloc(&c->d_stage, bytes));
-    c->stage_bytes = bytes;
+    HIP_TRY(c->d_stage.ensure(bytes));
     return 0;
 }
-
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
 } // namespace
 
@@ -1584,8 +1566,8 @@ int ezbch_destroy(ezbch_codec *c) {
     if (c->d_step) (void)hipFree(c->d_step);
     if (c->d_tabs) (void)hipFree(c->d_tabs);
     if (c->d_syn) (void)hipFree(c->d_syn);
-    if (c->d_stage) (void)hipFree(c->d_stage);
-    if (c->h_stage) (void)hipHostFree(c->h_stage);
+    c->d_stage.release();
+    c->h_stage.release();
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return 0;
@@ -1607,19 +1589,19 @@ int ezbch_encode(const ezbch_codec *c, const uint8_t *data, size_t data_stride, 
                  uint8_t *ecc, size_t ecc_stride, size_t ncw, void *stream) {
     if (!c) return -EINVAL;
     if (ncw == 0) return 0;
-    if (int r = check_args(c, data, data_stride, len, ecc, ecc_stride, ncw)) return r;
-    DeviceGuard g(c->device);
-    BchArgs a{data, nullptr, data_stride, len, ecc, ecc_stride, nullptr, nullptr, 0, ncw, 0};
-    hipError_t e = launch_encode(c->dev, a, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : hip_fail(e, "BCH encode launch");
+    if (int r = check_rows(c, data, data_stride, len, ecc, ecc_stride, ncw, false)) return r;
+    return run(c, BchArgs{data, nullptr, data_stride, len, ecc, ecc_stride, nullptr, nullptr, 0, ncw, 0},
+               false, stream);
 }
 
 int ezbch_encode_rows(const ezbch_codec *c, uint8_t *rows, size_t stride, unsigned len,
                       size_t ncw, void *stream) {
     if (!c) return -EINVAL;
     if (ncw == 0) return 0;
-    if (int r = check_rows(c, rows, stride, len, ncw)) return r;
-    return ezbch_encode(c, rows, stride, len, rows + len, stride, ncw, stream);
+    uint8_t *ecc = nullptr;
+    size_t ecc_stride = 0;
+    if (int r = check_rows(c, rows, stride, len, ecc, ecc_stride, ncw, true)) return r;
+    return ezbch_encode(c, rows, stride, len, ecc, ecc_stride, ncw, stream);
 }
 
 int ezbch_decode(const ezbch_codec *c, uint8_t *data, size_t data_stride, unsigned len,
@@ -1628,17 +1610,10 @@ int ezbch_decode(const ezbch_codec *c, uint8_t *data, size_t data_stride, unsign
     if (!c) return -EINVAL;
     if (ncw == 0) return 0;
     if (!result) return -EINVAL;
-    if (!ecc) {   // ECC inside the row
-        if (int r = check_rows(c, data, data_stride, len, ncw)) return r;
-        ecc = data + len;
-        ecc_stride = data_stride;
-    }
-    if (int r = check_args(c, data, data_stride, len, ecc, ecc_stride, ncw)) return r;
-    if (errloc && ncw > 1 && errloc_stride < c->h.t) return -EINVAL;
-    DeviceGuard g(c->device);
-    BchArgs a{data, data, data_stride, len, ecc, ecc_stride, result, errloc, errloc_stride, ncw, 0, 0};
-    hipError_t e = launch_decode(c->dev, a, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : hip_fail(e, "BCH decode launch");
+    if (int r = check_rows(c, data, data_stride, len, ecc, ecc_stride, ncw, true)) return r;
+    if (bad_errloc(c, errloc, errloc_stride, ncw)) return -EINVAL;
+    return run(c, BchArgs{data, data, data_stride, len, ecc, ecc_stride, result, errloc, errloc_stride,
+                          ncw, 0, 0}, true, stream);
 }
 
 int ezbch_decode_ecc(const ezbch_codec *c, const uint8_t *ecc, size_t ecc_stride, unsigned len,
@@ -1648,12 +1623,9 @@ int ezbch_decode_ecc(const ezbch_codec *c, const uint8_t *ecc, size_t ecc_stride
     if (ncw == 0) return 0;
     if (!result || !ecc) return -EINVAL;
     if (ncw > 1 && ecc_stride < c->h.ecc_bytes) return -EINVAL;
-    if (errloc && ncw > 1 && errloc_stride < c->h.t) return -EINVAL;
-    DeviceGuard g(c->device);
-    BchArgs a{nullptr, nullptr, 0, len, const_cast<uint8_t *>(ecc), ecc_stride, result, errloc,
-              errloc_stride, ncw, 0, 0, 1};
-    hipError_t e = launch_decode(c->dev, a, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : hip_fail(e, "BCH decode launch");
+    if (bad_errloc(c, errloc, errloc_stride, ncw)) return -EINVAL;
+    return run(c, BchArgs{nullptr, nullptr, 0, len, const_cast<uint8_t *>(ecc), ecc_stride, result, errloc,
+                          errloc_stride, ncw, 0, 0, 1}, true, stream);
 }
 
 int ezbch_decode_syn(const ezbch_codec *c, const uint32_t *syn, size_t syn_stride, unsigned len,
@@ -1663,12 +1635,9 @@ int ezbch_decode_syn(const ezbch_codec *c, const uint32_t *syn, size_t syn_strid
     if (ncw == 0) return 0;
     if (!result || !syn) return -EINVAL;
     if (ncw > 1 && syn_stride < 2 * (size_t)c->h.t) return -EINVAL;
-    if (errloc && ncw > 1 && errloc_stride < c->h.t) return -EINVAL;
-    DeviceGuard g(c->device);
-    BchArgs a{nullptr, nullptr, 0, len, nullptr, 0, result, errloc, errloc_stride, ncw, 0, 0, 1,
-              syn, syn_stride};
-    hipError_t e = launch_decode(c->dev, a, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : hip_fail(e, "BCH decode launch");
+    if (bad_errloc(c, errloc, errloc_stride, ncw)) return -EINVAL;
+    return run(c, BchArgs{nullptr, nullptr, 0, len, nullptr, 0, result, errloc, errloc_stride, ncw, 0, 0, 1,
+                          syn, syn_stride}, true, stream);
 }
 
 namespace {
@@ -1691,8 +1660,8 @@ int bch_encode_host_core(ezbch_codec *c, const uint8_t *data, size_t data_stride
     if (int r = ensure_stage(c, b_in + b_ecc)) return r;
     if (int r = ensure_hstage(c, (span ? 0 : align_up(chunk * len)) + (ecc_direct ? 0 : b_ecc) + 256))
         return r;
-    uint8_t *st = static_cast<uint8_t *>(c->d_stage), *dec = st + b_in;
-    uint8_t *hs = static_cast<uint8_t *>(c->h_stage);
+    uint8_t *st = static_cast<uint8_t *>(c->d_stage.p[0]), *dec = st + b_in;
+    uint8_t *hs = static_cast<uint8_t *>(c->h_stage.p[0]);
     uint8_t *hin = hs, *hecc = hs + (span ? 0 : align_up(chunk * len));
     for (size_t k0 = 0; k0 < ncw; k0 += chunk) {
         const size_t n = ncw - k0 < chunk ? ncw - k0 : chunk;
@@ -1720,7 +1689,7 @@ int ezbch_encode_host(ezbch_codec *c, const uint8_t *data, size_t data_stride, u
                       uint8_t *ecc, size_t ecc_stride, size_t ncw, size_t chunk) {
     if (!c) return -EINVAL;
     if (ncw == 0) return 0;
-    if (int r = check_args(c, data, data_stride, len, ecc, ecc_stride, ncw)) return r;
+    if (int r = check_rows(c, data, data_stride, len, ecc, ecc_stride, ncw, false)) return r;
     std::lock_guard<std::mutex> lk(c->mu);
     DeviceGuard g(c->device);
     return bch_encode_host_core(c, data, data_stride, len, ecc, ecc_stride, ncw, chunk);
@@ -1730,10 +1699,10 @@ int ezbch_encode_rows_host(ezbch_codec *c, uint8_t *rows, size_t stride, unsigne
                            size_t chunk) {
     if (!c) return -EINVAL;
     if (ncw == 0) return 0;
-    if (int r = check_rows(c, rows, stride, len, ncw)) return r;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    return bch_encode_host_core(c, rows, stride, len, rows + len, stride, ncw, chunk);
+    uint8_t *ecc = nullptr;
+    size_t ecc_stride = 0;
+    if (int r = check_rows(c, rows, stride, len, ecc, ecc_stride, ncw, true)) return r;
+    return ezbch_encode_host(c, rows, stride, len, ecc, ecc_stride, ncw, chunk);
 }
 
 int ezbch_decode_syn_host(ezbch_codec *c, const uint32_t *syn, size_t syn_stride, unsigned len,
@@ -1743,13 +1712,13 @@ int ezbch_decode_syn_host(ezbch_codec *c, const uint32_t *syn, size_t syn_stride
     if (!result || !syn) return -EINVAL;
     const size_t S = 2 * (size_t)c->h.t, T = c->h.t;
     if (ncw > 1 && syn_stride < S) return -EINVAL;
-    if (errloc && ncw > 1 && errloc_stride < T) return -EINVAL;
+    if (bad_errloc(c, errloc, errloc_stride, ncw)) return -EINVAL;
     if (ncw == 1) syn_stride = S, errloc_stride = T;
     std::lock_guard<std::mutex> lk(c->mu);
     DeviceGuard g(c->device);
     const size_t b_syn = align_up(ncw * S * 4), b_res = align_up(ncw * 4);
     if (int r = ensure_stage(c, b_syn + b_res + ncw * T * 4)) return r;
-    uint8_t *st = static_cast<uint8_t *>(c->d_stage);
+    uint8_t *st = static_cast<uint8_t *>(c->d_stage.p[0]);
     uint32_t *dsyn = reinterpret_cast<uint32_t *>(st);
     int32_t *dres = reinterpret_cast<int32_t *>(st + b_syn);
     uint32_t *dloc = reinterpret_cast<uint32_t *>(st + b_syn + b_res);
@@ -1769,13 +1738,8 @@ int ezbch_decode_host(ezbch_codec *c, uint8_t *data, size_t data_stride, unsigne
     if (!c) return -EINVAL;
     if (ncw == 0) return 0;
     if (!result) return -EINVAL;
-    if (!ecc) {
-        if (int r = check_rows(c, data, data_stride, len, ncw)) return r;
-        ecc = data + len;
-        ecc_stride = data_stride;
-    }
-    if (int r = check_args(c, data, data_stride, len, ecc, ecc_stride, ncw)) return r;
-    if (errloc && ncw > 1 && errloc_stride < c->h.t) return -EINVAL;
+    if (int r = check_rows(c, data, data_stride, len, ecc, ecc_stride, ncw, true)) return r;
+    if (bad_errloc(c, errloc, errloc_stride, ncw)) return -EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
     DeviceGuard g(c->device);
     const size_t eb = c->h.ecc_bytes, row = (size_t)len + eb, T = c->h.t;
@@ -1783,7 +1747,7 @@ int ezbch_decode_host(ezbch_codec *c, uint8_t *data, size_t data_stride, unsigne
     if (chunk > ncw) chunk = ncw;
     const size_t b_rows = align_up(chunk * row), b_res = align_up(chunk * 4);
     if (int r = ensure_stage(c, b_rows + b_res + align_up(errloc ? chunk * T * 4 : 0))) return r;
-    uint8_t *st = static_cast<uint8_t *>(c->d_stage);
+    uint8_t *st = static_cast<uint8_t *>(c->d_stage.p[0]);
     int32_t *dres = reinterpret_cast<int32_t *>(st + b_rows);
     uint32_t *dloc = reinterpret_cast<uint32_t *>(st + b_rows + b_res);
     for (size_t k0 = 0; k0 < ncw; k0 += chunk) {

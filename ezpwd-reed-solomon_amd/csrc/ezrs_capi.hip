@@ -18,6 +18,7 @@
 
 #include "../../include/ezrs.h"
 #include "ezrs_internal.hpp"
+#include "ezrs_host.hpp"
 
 using namespace ezrs;
 
@@ -28,10 +29,8 @@ struct ezrs_codec {
     uint16_t *d_tabs = nullptr;   // alpha_to | index_of | genpoly
     uint8_t *d_dual = nullptr;    // into_dual | from_dual
     std::mutex mu;                // guards the lazily grown host-pipeline buffers
-    void *h_stage[2] = {nullptr, nullptr};
-    void *d_stage[2] = {nullptr, nullptr};
-    size_t stage_bytes = 0;       // device bytes of each d_stage buffer
-    size_t hstage_bytes = 0;      // pinned host bytes of each h_stage buffer
+    StageBufs<2> d_stage;         // one per pipeline stream
+    StageBufs<2, hipHostMallocMapped> h_stage;   // device-visible: k_compact_rows writes here
     hipStream_t streams[2] = {nullptr, nullptr};
     int bs_id = -1;               // bit-sliced GF(2^8) kernel set, -1 if none
     int ps_id = -1;               // plane-sliced GF(2^8) kernel set, -1 if none
@@ -66,18 +65,7 @@ constexpr size_t kReconMaxTable = (size_t)64 << 20;   // bytes of a plan's devic
 
 thread_local std::string g_last_error;
 
-int hip_fail(hipError_t e, const char *what) {
-    g_last_error = std::string(what) + ": " + hipGetErrorString(e);
-    if (e == hipErrorOutOfMemory) return -ENOMEM;
-    if (e == hipErrorNoDevice || e == hipErrorInvalidDevice) return -ENODEV;
-    return -EIO;
-}
-
-#define HIP_TRY(expr)                                          \
-    do {                                                       \
-        hipError_t e_ = (expr);                                \
-        if (e_ != hipSuccess) return hip_fail(e_, #expr);      \
-    } while (0)
+int hip_fail(hipError_t e, const char *what) { return ezrs::hip_fail(g_last_error, e, what); }
 
 // Standard field polynomial per symbol size (rs:75-89).
 unsigned std_poly(unsigned mm) {
@@ -85,17 +73,6 @@ unsigned std_poly(unsigned mm) {
                                    0x805, 0x1053, 0x201b, 0x4443, 0x8003, 0x1100b};
     return mm <= 16 ? p[mm] : 0;
 }
-
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
 
 } // namespace
 
@@ -223,11 +200,10 @@ int ezrs_destroy(ezrs_codec *c) {
     if (c->d_wcols) (void)hipFree(c->d_wcols);
     for (auto &kv : c->ws) (void)hipFree(kv.second.p);
     for (void *p : c->ws_retired) (void)hipFree(p);
-    for (int i = 0; i < 2; ++i) {
-        if (c->d_stage[i]) (void)hipFree(c->d_stage[i]);
-        if (c->h_stage[i]) (void)hipHostFree(c->h_stage[i]);
+    c->d_stage.release();
+    c->h_stage.release();
+    for (int i = 0; i < 2; ++i)
         if (c->streams[i]) (void)hipStreamDestroy(c->streams[i]);
-    }
     delete c;
     return 0;
 }
@@ -269,7 +245,7 @@ int ezrs_get_info(const ezrs_codec *c, ezrs_info *info) {
     info->poly = m.spec.poly;
     info->fcr = m.spec.fcr;
     info->prim = m.spec.prim;
-    info->datum_bytes = m.spec.mm <= 8 ? 1 : 2;
+    info->datum_bytes = sym_bytes(c->dev);
     info->dual = m.spec.dual;
     info->device = c->device;
     return 0;
@@ -321,7 +297,7 @@ hipError_t dispatch_encode(const ezrs_codec *c, const EncodeArgs &a, void *ws, h
 // syn_ws: the sliced paths' syndrome workspace (ws_bytes_for).
 hipError_t dispatch_decode(const ezrs_codec *c, const DecodeArgs &a, uint8_t *syn_ws,
                            hipStream_t st) {
-    const unsigned w = c->dev.mm <= 8 ? 1 : 2;
+    const unsigned w = sym_bytes(c->dev);
     const bool contiguous = a.parity == static_cast<char *>(a.data) + (size_t)a.len * w &&
                             a.parity_stride == a.data_stride;
     if (c->ps_id >= 0 && ps_can_decode(c->dev, a)) {
@@ -366,55 +342,108 @@ size_t ezrs_workspace_bytes(const ezrs_codec *c, size_t ncw) {
 
 namespace {
 
-// Argument checks of encode<INP> (rs_base:868-904) for a batch with a separate parity array.
-int check_encode(const ezrs_codec *c, const void *data, size_t data_stride, unsigned len,
-                 const void *parity, size_t parity_stride, size_t ncw) {
-    if (!c || !data || !parity) return -EINVAL;
-    if (len < 1 || len > c->dev.load) return -EINVAL;                 // rs_base:875-877
-    if (ncw > 1 && (parity_stride < c->dev.nroots || data_stride < len)) return -EINVAL;
-    return 0;
-}
-
-// Row form (rs_base:778-790): the parity follows the data in each row.
-int check_rows(const ezrs_codec *c, const void *rows, size_t stride, unsigned len, size_t ncw) {
-    if (!c || !rows) return -EINVAL;
-    if (len < 1 || len > c->dev.load) return -EINVAL;
-    if (ncw > 1 && stride < (size_t)len + c->dev.nroots) return -EINVAL;
-    return 0;
-}
-
-int encode_dev(const ezrs_codec *c, const void *data, size_t data_stride, unsigned len,
-               void *parity, size_t parity_stride, size_t ncw, void *ws, size_t ws_bytes,
-               void *stream) {
-    if (ws_bytes < ws_bytes_for(c, ncw) || (ws_bytes && !ws)) return -EINVAL;
-    DeviceGuard g(c->device);
-    EncodeArgs a{data, data_stride, len, parity, parity_stride, ncw};
-    hipError_t e = dispatch_encode(c, a, ws, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "encode launch");
-    return 0;
-}
-
-int check_decode(const ezrs_codec *c, void *data, size_t data_stride, unsigned len,
-                 void *&parity, size_t &parity_stride, const uint32_t *eras, size_t eras_stride,
-                 const uint32_t *neras, int32_t *result, uint32_t *positions, size_t pos_stride,
-                 void *corr, size_t corr_stride, size_t ncw) {
-    if (!c || !data || !result) return -EINVAL;
-    const unsigned w = c->dev.mm <= 8 ? 1 : 2;
+// Row geometry of a batch: the argument checks of encode<INP> / decode<INP> (rs_base:868-904,
+// 1170-1242).  parity == NULL is the row form (rs_base:778-790), legal where row_form is set: the
+// parity follows the data in each row, and parity / parity_stride are resolved to it.  The stride
+// rules hold for ncw > 1 only (one codeword may pass any stride, 0 included).
+int check_rows(const ezrs_codec *c, const void *data, size_t data_stride, unsigned len,
+               void *&parity, size_t &parity_stride, size_t ncw, bool row_form) {
+    if (!data || (!parity && !row_form)) return -EINVAL;
     const unsigned NR = c->dev.nroots;
-    if (len < 1 || len > c->dev.load) return -EINVAL;
+    if (len < 1 || len > c->dev.load) return -EINVAL;                 // rs_base:875-877
     if (!parity) {
-        parity = static_cast<char *>(data) + (size_t)len * w;
+        parity = static_cast<char *>(const_cast<void *>(data)) + (size_t)len * sym_bytes(c->dev);
         parity_stride = data_stride;
         if (ncw > 1 && data_stride < (size_t)len + NR) return -EINVAL;
     } else if (ncw > 1 && parity_stride < NR) {
         return -EINVAL;
     }
     if (ncw > 1 && data_stride < len) return -EINVAL;
-    if (neras && !eras) return -EINVAL;
-    if (eras && ncw > 1 && eras_stride == 0) return -EINVAL;
-    if (positions && ncw > 1 && pos_stride < NR) return -EINVAL;
-    if (corr && ncw > 1 && corr_stride < NR) return -EINVAL;
     return 0;
+}
+
+// What a decode returns per codeword, and the erasures it takes (strides in elements; ezrs_decode).
+struct DecodeOut {
+    const uint32_t *eras;
+    size_t eras_stride;
+    const uint32_t *neras;
+    int32_t *result;
+    uint32_t *positions;
+    size_t pos_stride;
+    void *corr;
+    size_t corr_stride;
+
+    // Decode of n codewords whose rows are given as they lie (data, parity) and whose outputs are
+    // entries k0 .. k0 + n - 1 of this.  One codeword: a zero stride is harmless (row 0 only).
+    DecodeArgs args(const ezrs_codec *c, void *data, size_t data_stride, unsigned len, void *parity,
+                    size_t parity_stride, size_t k0, size_t n, const Shards &sh = {}) const {
+        return {data, data_stride, len, parity, parity_stride,
+                eras ? eras + k0 * eras_stride : nullptr, eras_stride, neras ? neras + k0 : nullptr,
+                result + k0, positions ? positions + k0 * pos_stride : nullptr, pos_stride,
+                corr ? static_cast<char *>(corr) + k0 * corr_stride * sym_bytes(c->dev) : nullptr,
+                corr_stride, n, sh};
+    }
+};
+
+int check_decode_out(const ezrs_codec *c, size_t ncw, const DecodeOut &o) {
+    const unsigned NR = c->dev.nroots;
+    if (!o.result) return -EINVAL;
+    if (o.neras && !o.eras) return -EINVAL;
+    if (o.eras && ncw > 1 && o.eras_stride == 0) return -EINVAL;
+    if (o.positions && ncw > 1 && o.pos_stride < NR) return -EINVAL;
+    if (o.corr && ncw > 1 && o.corr_stride < NR) return -EINVAL;
+    return 0;
+}
+
+// A workspace the caller owns (the _ws forms); the other forms use the calling stream's.
+struct CallerWs {
+    void *p;
+    size_t bytes;
+};
+
+int take_ws(const ezrs_codec *c, const CallerWs *cw, size_t need, void *stream, void **ws) {
+    if (!cw) return stream_ws(c, stream, need, ws);
+    *ws = cw->p;
+    return cw->bytes < need || (cw->bytes && !cw->p) ? -EINVAL : 0;
+}
+
+int run_encode(const ezrs_codec *c, const EncodeArgs &a, void *ws, void *stream) {
+    hipError_t e = dispatch_encode(c, a, ws, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : hip_fail(e, "encode launch");
+}
+
+int run_decode(const ezrs_codec *c, const DecodeArgs &a, void *ws, void *stream) {
+    hipError_t e = dispatch_decode(c, a, static_cast<uint8_t *>(ws), static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : hip_fail(e, "decode launch");
+}
+
+// One checked batch on the device (the encode `ea`, or else the decode `da`): the codec's device,
+// the workspace, the kernels.
+int run_batch(const ezrs_codec *c, const EncodeArgs *ea, const DecodeArgs *da, const CallerWs *cw,
+              void *stream) {
+    DeviceGuard g(c->device);
+    void *ws = nullptr;
+    if (int r = take_ws(c, cw, ws_bytes_for(c, ea ? ea->ncw : da->ncw), stream, &ws)) return r;
+    return ea ? run_encode(c, *ea, ws, stream) : run_decode(c, *da, ws, stream);
+}
+
+int encode_dev(const ezrs_codec *c, const void *data, size_t data_stride, unsigned len, void *parity,
+               size_t parity_stride, size_t ncw, bool row_form, const CallerWs *cw, void *stream) {
+    if (!c) return -EINVAL;
+    if (ncw == 0) return 0;
+    if (int r = check_rows(c, data, data_stride, len, parity, parity_stride, ncw, row_form)) return r;
+    const EncodeArgs a{data, data_stride, len, parity, parity_stride, ncw};
+    return run_batch(c, &a, nullptr, cw, stream);
+}
+
+int decode_dev(const ezrs_codec *c, void *data, size_t data_stride, unsigned len, void *parity,
+               size_t parity_stride, const DecodeOut &o, size_t ncw, const CallerWs *cw, void *stream) {
+    if (!c) return -EINVAL;
+    if (ncw == 0) return 0;
+    if (int r = check_rows(c, data, data_stride, len, parity, parity_stride, ncw, true)) return r;
+    if (int r = check_decode_out(c, ncw, o)) return r;
+    const DecodeArgs a = o.args(c, data, data_stride, len, parity, parity_stride, 0, ncw);
+    return run_batch(c, nullptr, &a, cw, stream);
 }
 
 } // namespace
@@ -422,44 +451,24 @@ int check_decode(const ezrs_codec *c, void *data, size_t data_stride, unsigned l
 int ezrs_encode_ws(const ezrs_codec *c, const void *data, size_t data_stride, unsigned len,
                    void *parity, size_t parity_stride, size_t ncw, void *ws, size_t ws_bytes,
                    void *stream) {
-    if (!c) return -EINVAL;
-    if (ncw == 0) return 0;
-    if (int r = check_encode(c, data, data_stride, len, parity, parity_stride, ncw)) return r;
-    return encode_dev(c, data, data_stride, len, parity, parity_stride, ncw, ws, ws_bytes, stream);
+    const CallerWs cw{ws, ws_bytes};
+    return encode_dev(c, data, data_stride, len, parity, parity_stride, ncw, false, &cw, stream);
 }
 
 int ezrs_encode(const ezrs_codec *c, const void *data, size_t data_stride, unsigned len,
                 void *parity, size_t parity_stride, size_t ncw, void *stream) {
-    if (!c) return -EINVAL;
-    if (ncw == 0) return 0;
-    if (int r = check_encode(c, data, data_stride, len, parity, parity_stride, ncw)) return r;
-    DeviceGuard g(c->device);
-    const size_t need = ws_bytes_for(c, ncw);
-    void *ws = nullptr;
-    if (int r = stream_ws(c, stream, need, &ws)) return r;
-    return encode_dev(c, data, data_stride, len, parity, parity_stride, ncw, ws, need, stream);
+    return encode_dev(c, data, data_stride, len, parity, parity_stride, ncw, false, nullptr, stream);
 }
 
 int ezrs_encode_rows_ws(const ezrs_codec *c, void *rows, size_t stride, unsigned len, size_t ncw,
                         void *ws, size_t ws_bytes, void *stream) {
-    if (!c) return -EINVAL;
-    if (ncw == 0) return 0;
-    if (int r = check_rows(c, rows, stride, len, ncw)) return r;
-    char *r0 = static_cast<char *>(rows);
-    const size_t w = c->dev.mm <= 8 ? 1 : 2;
-    return encode_dev(c, r0, stride, len, r0 + (size_t)len * w, stride, ncw, ws, ws_bytes, stream);
+    const CallerWs cw{ws, ws_bytes};
+    return encode_dev(c, rows, stride, len, nullptr, 0, ncw, true, &cw, stream);
 }
 
 int ezrs_encode_rows(const ezrs_codec *c, void *rows, size_t stride, unsigned len, size_t ncw,
                      void *stream) {
-    if (!c) return -EINVAL;
-    if (ncw == 0) return 0;
-    if (int r = check_rows(c, rows, stride, len, ncw)) return r;
-    DeviceGuard g(c->device);
-    const size_t need = ws_bytes_for(c, ncw);
-    void *ws = nullptr;
-    if (int r = stream_ws(c, stream, need, &ws)) return r;
-    return ezrs_encode_rows_ws(c, rows, stride, len, ncw, ws, need, stream);
+    return encode_dev(c, rows, stride, len, nullptr, 0, ncw, true, nullptr, stream);
 }
 
 int ezrs_decode_ws(const ezrs_codec *c, void *data, size_t data_stride, unsigned len,
@@ -467,34 +476,19 @@ int ezrs_decode_ws(const ezrs_codec *c, void *data, size_t data_stride, unsigned
                    const uint32_t *neras, int32_t *result, uint32_t *positions, size_t pos_stride,
                    void *corr, size_t corr_stride, size_t ncw, void *ws, size_t ws_bytes,
                    void *stream) {
-    if (!c) return -EINVAL;
-    if (ncw == 0) return 0;
-    if (int r = check_decode(c, data, data_stride, len, parity, parity_stride, eras, eras_stride,
-                             neras, result, positions, pos_stride, corr, corr_stride, ncw))
-        return r;
-    if (ws_bytes < ws_bytes_for(c, ncw) || (ws_bytes && !ws)) return -EINVAL;
-    DeviceGuard g(c->device);
-    // one codeword: a zero eras_stride is harmless (row 0 only)
-    DecodeArgs a{data, data_stride, len, parity, parity_stride, eras, eras_stride, neras,
-                 result, positions, pos_stride, corr, corr_stride, ncw};
-    hipError_t e = dispatch_decode(c, a, static_cast<uint8_t *>(ws), static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "decode launch");
-    return 0;
+    const CallerWs cw{ws, ws_bytes};
+    return decode_dev(c, data, data_stride, len, parity, parity_stride,
+                      {eras, eras_stride, neras, result, positions, pos_stride, corr, corr_stride}, ncw,
+                      &cw, stream);
 }
 
 int ezrs_decode(const ezrs_codec *c, void *data, size_t data_stride, unsigned len, void *parity,
                 size_t parity_stride, const uint32_t *eras, size_t eras_stride,
                 const uint32_t *neras, int32_t *result, uint32_t *positions, size_t pos_stride,
                 void *corr, size_t corr_stride, size_t ncw, void *stream) {
-    if (!c) return -EINVAL;
-    if (ncw == 0) return 0;
-    DeviceGuard g(c->device);
-    const size_t need = ws_bytes_for(c, ncw);
-    void *ws = nullptr;
-    if (int r = stream_ws(c, stream, need, &ws)) return r;
-    return ezrs_decode_ws(c, data, data_stride, len, parity, parity_stride, eras, eras_stride,
-                          neras, result, positions, pos_stride, corr, corr_stride, ncw, ws, need,
-                          stream);
+    return decode_dev(c, data, data_stride, len, parity, parity_stride,
+                      {eras, eras_stride, neras, result, positions, pos_stride, corr, corr_stride}, ncw,
+                      nullptr, stream);
 }
 
 // ---- shard batches -----------------------------------------------------------------------------
@@ -530,17 +524,10 @@ int ezrs_encode_shards(const ezrs_codec *c, void *shards, size_t shard_pitch, si
     Shards g;
     if (!c || !shards || !shard_geom(c, shard_len, chunk, shard_pitch, g)) return -EINVAL;
     if (nshards == 0) return 0;
-    const size_t w = c->dev.mm <= 8 ? 1 : 2, ncw = nshards * g.rows;
-    DeviceGuard dg(c->device);
-    const size_t need = ws_bytes_for(c, ncw);
-    void *ws = nullptr;
-    if (int r = stream_ws(c, stream, need, &ws)) return r;
+    const size_t row = (size_t)chunk + c->dev.nroots;
     char *r0 = static_cast<char *>(shards);
-    EncodeArgs a{r0, (size_t)chunk + c->dev.nroots, chunk, r0 + (size_t)chunk * w,
-                 (size_t)chunk + c->dev.nroots, ncw, g};
-    hipError_t e = dispatch_encode(c, a, ws, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "encode launch");
-    return 0;
+    const EncodeArgs a{r0, row, chunk, r0 + (size_t)chunk * sym_bytes(c->dev), row, nshards * g.rows, g};
+    return run_batch(c, &a, nullptr, nullptr, stream);
 }
 
 int ezrs_decode_shards(const ezrs_codec *c, void *shards, size_t shard_pitch, size_t shard_len,
@@ -550,22 +537,12 @@ int ezrs_decode_shards(const ezrs_codec *c, void *shards, size_t shard_pitch, si
     Shards g;
     if (!c || !shards || !result || !shard_geom(c, shard_len, chunk, shard_pitch, g)) return -EINVAL;
     if (nshards == 0) return 0;
-    const unsigned NR = c->dev.nroots;
-    const size_t w = c->dev.mm <= 8 ? 1 : 2, ncw = nshards * g.rows;
-    if (neras && !eras) return -EINVAL;
-    if (eras && ncw > 1 && eras_stride == 0) return -EINVAL;
-    if (positions && ncw > 1 && pos_stride < NR) return -EINVAL;
-    if (corr && ncw > 1 && corr_stride < NR) return -EINVAL;
-    DeviceGuard dg(c->device);
-    const size_t need = ws_bytes_for(c, ncw);
-    void *ws = nullptr;
-    if (int r = stream_ws(c, stream, need, &ws)) return r;
+    const DecodeOut o{eras, eras_stride, neras, result, positions, pos_stride, corr, corr_stride};
+    const size_t row = (size_t)chunk + c->dev.nroots, ncw = nshards * g.rows;
+    if (int r = check_decode_out(c, ncw, o)) return r;
     char *r0 = static_cast<char *>(shards);
-    DecodeArgs a{r0, (size_t)chunk + NR, chunk, r0 + (size_t)chunk * w, (size_t)chunk + NR, eras,
-                 eras_stride, neras, result, positions, pos_stride, corr, corr_stride, ncw, g};
-    hipError_t e = dispatch_decode(c, a, static_cast<uint8_t *>(ws), static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "decode launch");
-    return 0;
+    const DecodeArgs a = o.args(c, r0, row, chunk, r0 + (size_t)chunk * sym_bytes(c->dev), row, 0, ncw, g);
+    return run_batch(c, nullptr, &a, nullptr, stream);
 }
 
 // ---- interleaved frames ------------------------------------------------------------------------
@@ -575,7 +552,7 @@ namespace {
 // Cache (EZRS_IL_STAGE_MB, default 64; 0 = the whole batch in one pass, for A/B measurements),
 // capped by the launch_rows test hook rounded up to whole tiles.
 size_t il_chunk_rows(const ezrs_codec *c, unsigned len, size_t ncw) {
-    const size_t w = c->dev.mm <= 8 ? 1 : 2, row = ((size_t)len + c->dev.nroots) * w;
+    const size_t w = sym_bytes(c->dev), row = ((size_t)len + c->dev.nroots) * w;
     size_t n = ncw < kIlMaxRows ? ncw : kIlMaxRows;
     const char *e = getenv("EZRS_IL_STAGE_MB");
     const size_t mb = e ? (size_t)strtoull(e, nullptr, 10) : 64;
@@ -598,7 +575,7 @@ size_t il_chunk_rows(const ezrs_codec *c, unsigned len, size_t ncw) {
 // Workspace of an interleaved call: the codec's own region for one pass, then the staged rows.
 size_t il_ws_codec(const ezrs_codec *c, size_t chunk) { return (ws_bytes_for(c, chunk) + 255) & ~(size_t)255; }
 size_t il_ws_bytes(const ezrs_codec *c, unsigned len, size_t ncw) {
-    const size_t w = c->dev.mm <= 8 ? 1 : 2, chunk = il_chunk_rows(c, len, ncw);
+    const size_t w = sym_bytes(c->dev), chunk = il_chunk_rows(c, len, ncw);
     return il_ws_codec(c, chunk) + il_stage_bytes(chunk, (size_t)len + c->dev.nroots, w);
 }
 
@@ -614,27 +591,17 @@ int il_check(const ezrs_codec *c, const void *frames, size_t frame_pitch, size_t
     return 0;
 }
 
-struct IlDecode {
-    const uint32_t *eras;
-    size_t eras_stride;
-    const uint32_t *neras;
-    int32_t *result;
-    uint32_t *positions;
-    size_t pos_stride;
-    void *corr;
-    size_t corr_stride;
-};
-
 // Both directions, pass by pass: gather, the codec's row kernels on the staged rows, scatter.
 //   encode (dec == null): gather the data symbols, scatter the parity symbols of every codeword
 //   decode: gather whole codewords, scatter whole rows of the codewords whose result is nonzero
 int il_run(const ezrs_codec *c, void *frames, size_t frame_pitch, size_t sym_stride, size_t depth,
-           unsigned len, size_t ncw, const IlDecode *dec, void *ws, size_t ws_bytes, void *stream) {
-    if (ws_bytes < il_ws_bytes(c, len, ncw) || !ws) return -EINVAL;
+           unsigned len, size_t ncw, const DecodeOut *dec, const CallerWs *cw, void *stream) {
     DeviceGuard g(c->device);
+    void *ws = nullptr;
+    if (int r = take_ws(c, cw, il_ws_bytes(c, len, ncw), stream, &ws)) return r;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const unsigned NR = c->dev.nroots;
-    const size_t w = c->dev.mm <= 8 ? 1 : 2, P = (size_t)len + NR;
+    const size_t w = sym_bytes(c->dev), P = (size_t)len + NR;
     const size_t chunk = il_chunk_rows(c, len, ncw);
     if (ncw == depth) frame_pitch = 0;              // one frame: its pitch is not used
     char *stage =static_cast<char *>(ws) + il_ws_codec(c, chunk);
@@ -645,19 +612,13 @@ int il_run(const ezrs_codec *c, void *frames, size_t frame_pitch, size_t sym_str
         hipError_t e = launch_il_gather(c->dev, a, st);
         if (e != hipSuccess) return hip_fail(e, "interleaved gather launch");
         if (!dec) {
-            EncodeArgs ea{stage, P, len, stage + (size_t)len * w, P, n};
-            if ((e = dispatch_encode(c, ea, ws, st)) != hipSuccess) return hip_fail(e, "encode launch");
+            if (int r = run_encode(c, EncodeArgs{stage, P, len, stage + (size_t)len * w, P, n}, ws, stream))
+                return r;
             a.s0 = len;
             a.s1 = len + NR;
         } else {
-            DecodeArgs da{stage, P, len, stage + (size_t)len * w, P,
-                          dec->eras ? dec->eras + k0 * dec->eras_stride : nullptr, dec->eras_stride,
-                          dec->neras ? dec->neras + k0 : nullptr, dec->result + k0,
-                          dec->positions ? dec->positions + k0 * dec->pos_stride : nullptr, dec->pos_stride,
-                          dec->corr ? static_cast<char *>(dec->corr) + k0 * dec->corr_stride * w : nullptr,
-                          dec->corr_stride, n};
-            if ((e = dispatch_decode(c, da, static_cast<uint8_t *>(ws), st)) != hipSuccess)
-                return hip_fail(e, "decode launch");
+            if (int r = run_decode(c, dec->args(c, stage, P, len, stage + (size_t)len * w, P, k0, n), ws, stream))
+                return r;
             a.result = dec->result + k0;
         }
         if ((e = launch_il_scatter(c->dev, a, st)) != hipSuccess) return hip_fail(e, "interleaved scatter launch");
@@ -665,14 +626,16 @@ int il_run(const ezrs_codec *c, void *frames, size_t frame_pitch, size_t sym_str
     return 0;
 }
 
-int il_check_decode(const ezrs_codec *c, size_t ncw, const IlDecode &d) {
-    const unsigned NR = c->dev.nroots;
-    if (!d.result) return -EINVAL;
-    if (d.neras && !d.eras) return -EINVAL;
-    if (d.eras && ncw > 1 && d.eras_stride == 0) return -EINVAL;
-    if (d.positions && ncw > 1 && d.pos_stride < NR) return -EINVAL;
-    if (d.corr && ncw > 1 && d.corr_stride < NR) return -EINVAL;
-    return 0;
+// The four interleaved entry points: dec == null encodes; cw == null uses the stream's workspace.
+int il_call(const ezrs_codec *c, void *frames, size_t frame_pitch, size_t sym_stride, size_t depth,
+            unsigned len, size_t nframes, const DecodeOut *dec, const CallerWs *cw, void *stream) {
+    if (!c) return -EINVAL;
+    if (nframes == 0) return 0;
+    size_t ncw;
+    if (int r = il_check(c, frames, frame_pitch, sym_stride, depth, len, nframes, ncw)) return r;
+    if (dec)
+        if (int r = check_decode_out(c, ncw, *dec)) return r;
+    return il_run(c, frames, frame_pitch, sym_stride, depth, len, ncw, dec, cw, stream);
 }
 
 } // namespace
@@ -686,24 +649,13 @@ size_t ezrs_interleaved_workspace_bytes(const ezrs_codec *c, unsigned len, size_
 int ezrs_encode_interleaved_ws(const ezrs_codec *c, void *frames, size_t frame_pitch, size_t sym_stride,
                                size_t depth, unsigned len, size_t nframes, void *ws, size_t ws_bytes,
                                void *stream) {
-    if (!c) return -EINVAL;
-    if (nframes == 0) return 0;
-    size_t ncw;
-    if (int r = il_check(c, frames, frame_pitch, sym_stride, depth, len, nframes, ncw)) return r;
-    return il_run(c, frames, frame_pitch, sym_stride, depth, len, ncw, nullptr, ws, ws_bytes, stream);
+    const CallerWs cw{ws, ws_bytes};
+    return il_call(c, frames, frame_pitch, sym_stride, depth, len, nframes, nullptr, &cw, stream);
 }
 
 int ezrs_encode_interleaved(const ezrs_codec *c, void *frames, size_t frame_pitch, size_t sym_stride,
                             size_t depth, unsigned len, size_t nframes, void *stream) {
-    if (!c) return -EINVAL;
-    if (nframes == 0) return 0;
-    size_t ncw;
-    if (int r = il_check(c, frames, frame_pitch, sym_stride, depth, len, nframes, ncw)) return r;
-    DeviceGuard g(c->device);
-    const size_t need = il_ws_bytes(c, len, ncw);
-    void *ws = nullptr;
-    if (int r = stream_ws(c, stream, need, &ws)) return r;
-    return il_run(c, frames, frame_pitch, sym_stride, depth, len, ncw, nullptr, ws, need, stream);
+    return il_call(c, frames, frame_pitch, sym_stride, depth, len, nframes, nullptr, nullptr, stream);
 }
 
 int ezrs_decode_interleaved_ws(const ezrs_codec *c, void *frames, size_t frame_pitch, size_t sym_stride,
@@ -711,13 +663,9 @@ int ezrs_decode_interleaved_ws(const ezrs_codec *c, void *frames, size_t frame_p
                                size_t eras_stride, const uint32_t *neras, int32_t *result,
                                uint32_t *positions, size_t pos_stride, void *corr, size_t corr_stride,
                                void *ws, size_t ws_bytes, void *stream) {
-    if (!c) return -EINVAL;
-    if (nframes == 0) return 0;
-    size_t ncw;
-    if (int r = il_check(c, frames, frame_pitch, sym_stride, depth, len, nframes, ncw)) return r;
-    const IlDecode d{eras, eras_stride, neras, result, positions, pos_stride, corr, corr_stride};
-    if (int r = il_check_decode(c, ncw, d)) return r;
-    return il_run(c, frames, frame_pitch, sym_stride, depth, len, ncw, &d, ws, ws_bytes, stream);
+    const DecodeOut o{eras, eras_stride, neras, result, positions, pos_stride, corr, corr_stride};
+    const CallerWs cw{ws, ws_bytes};
+    return il_call(c, frames, frame_pitch, sym_stride, depth, len, nframes, &o, &cw, stream);
 }
 
 int ezrs_decode_interleaved(const ezrs_codec *c, void *frames, size_t frame_pitch, size_t sym_stride,
@@ -725,17 +673,8 @@ int ezrs_decode_interleaved(const ezrs_codec *c, void *frames, size_t frame_pitc
                             size_t eras_stride, const uint32_t *neras, int32_t *result,
                             uint32_t *positions, size_t pos_stride, void *corr, size_t corr_stride,
                             void *stream) {
-    if (!c) return -EINVAL;
-    if (nframes == 0) return 0;
-    size_t ncw;
-    if (int r = il_check(c, frames, frame_pitch, sym_stride, depth, len, nframes, ncw)) return r;
-    const IlDecode d{eras, eras_stride, neras, result, positions, pos_stride, corr, corr_stride};
-    if (int r = il_check_decode(c, ncw, d)) return r;
-    DeviceGuard g(c->device);
-    const size_t need = il_ws_bytes(c, len, ncw);
-    void *ws = nullptr;
-    if (int r = stream_ws(c, stream, need, &ws)) return r;
-    return il_run(c, frames, frame_pitch, sym_stride, depth, len, ncw, &d, ws, need, stream);
+    const DecodeOut o{eras, eras_stride, neras, result, positions, pos_stride, corr, corr_stride};
+    return il_call(c, frames, frame_pitch, sym_stride, depth, len, nframes, &o, nullptr, stream);
 }
 
 // ---- shared-erasure reconstruction --------------------------------------------------------------
@@ -864,28 +803,10 @@ int ensure_stage(ezrs_codec *c, size_t dbytes, size_t hbytes) {
     if (!c->streams[0])
         for (int i = 0; i < 2; ++i)
             HIP_TRY(hipStreamCreateWithFlags(&c->streams[i], hipStreamNonBlocking));
-    if (c->stage_bytes < dbytes) {
-        for (int i = 0; i < 2; ++i) {
-            if (c->d_stage[i]) (void)hipFree(c->d_stage[i]);
-            c->d_stage[i] = nullptr;
-        }
-        c->stage_bytes = 0;
-        for (int i = 0; i < 2; ++i) HIP_TRY(hipMalloc(&c->d_stage[i], dbytes));
-        c->stage_bytes = dbytes;
-    }
-    if (c->hstage_bytes < hbytes) {
-        for (int i = 0; i < 2; ++i) {
-            if (c->h_stage[i]) (void)hipHostFree(c->h_stage[i]);
-            c->h_stage[i] = nullptr;
-        }
-        c->hstage_bytes = 0;
-        for (int i = 0; i < 2; ++i) HIP_TRY(hipHostMalloc(&c->h_stage[i], hbytes, hipHostMallocMapped));   // device-visible: k_compact_rows writes here
-        c->hstage_bytes = hbytes;
-    }
+    HIP_TRY(c->d_stage.ensure(dbytes));
+    HIP_TRY(c->h_stage.ensure(hbytes));
     return 0;
 }
-
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // Host threads for the CPU-side scatters of the host-memory forms (EZRS_HOST_THREADS, default 8).
 size_t host_threads() {
@@ -924,8 +845,8 @@ size_t default_chunk(size_t row_bytes, bool pinned = true) {
 //   rows != NULL: the rs_base:778-790 row form, parity at rows + len (data is rows)
 int encode_host_core(ezrs_codec *c, const char *data, size_t data_stride, unsigned len,
                      char *parity, size_t parity_stride, size_t ncw, size_t chunk) {
-    const size_t w = c->dev.mm <= 8 ? 1 : 2, NR = c->dev.nroots;
-    const size_t need = (size_t)len;                               // symbols a row must carry over
+    const size_t w = sym_bytes(c->dev), NR = c->dev.nroots;
+    const size_t need = (size_t)len;                              // symbols a row must carry over
     const bool span = ncw == 1 || data_stride <= 2 * need + NR;    // linear copy of the rows' span
     // device row pitch (symbols); a single row is staged at pitch len whatever its stride (a stride
     // below len, 0 included, is legal for one codeword and must not size the staging)
@@ -942,7 +863,7 @@ int encode_host_core(ezrs_codec *c, const char *data, size_t data_stride, unsign
     // single thread writing 32-byte pieces into 1 M rows takes ~5 ms, 2x the copy itself)
     auto scatter = [&](int s) {
         if (!pend[s].live || par_direct) return;
-        const char *src = static_cast<const char *>(c->h_stage[s]) + h_in;
+        const char *src = static_cast<const char *>(c->h_stage.p[s]) + h_in;
         const size_t n = pend[s].n, k0 = pend[s].k0;
         auto part = [&](size_t r0, size_t r1) {
             for (size_t r = r0; r < r1; ++r)
@@ -967,8 +888,8 @@ int encode_host_core(ezrs_codec *c, const char *data, size_t data_stride, unsign
             scatter(s);
             pend[s].live = false;
         }
-        char *d_in = static_cast<char *>(c->d_stage[s]), *d_par = d_in + b_in, *d_ws = d_par + b_par;
-        char *hs = static_cast<char *>(c->h_stage[s]);
+        char *d_in = static_cast<char *>(c->d_stage.p[s]), *d_par = d_in + b_in, *d_ws = d_par + b_par;
+        char *hs = static_cast<char *>(c->h_stage.p[s]);
         const char *hd = data + k0 * data_stride * w;
         if (span) {
             HIP_TRY(hipMemcpyAsync(d_in, hd, ((n - 1) * data_stride + need) * w,
@@ -998,7 +919,7 @@ int ezrs_encode_host(ezrs_codec *c, const void *data, size_t data_stride, unsign
                      void *parity, size_t parity_stride, size_t ncw, size_t chunk) {
     if (!c) return -EINVAL;
     if (ncw == 0) return 0;
-    if (int r = check_encode(c, data, data_stride, len, parity, parity_stride, ncw)) {
+    if (int r = check_rows(c, data, data_stride, len, parity, parity_stride, ncw, false)) {
         if (!parity)
             g_last_error = "ezrs_encode_host: parity is required (rows that carry their own parity: "
                            "ezrs_encode_rows_host)";
@@ -1014,12 +935,13 @@ int ezrs_encode_rows_host(ezrs_codec *c, void *rows, size_t stride, unsigned len
                           size_t chunk) {
     if (!c) return -EINVAL;
     if (ncw == 0) return 0;
-    if (int r0 = check_rows(c, rows, stride, len, ncw)) return r0;
-    const size_t w = c->dev.mm <= 8 ? 1 : 2;
+    void *parity = nullptr;
+    size_t parity_stride = 0;
+    if (int r = check_rows(c, rows, stride, len, parity, parity_stride, ncw, true)) return r;
     std::lock_guard<std::mutex> lk(c->mu);
     DeviceGuard g(c->device);
-    char *r = static_cast<char *>(rows);
-    return encode_host_core(c, r, stride, len, r + (size_t)len * w, stride, ncw, chunk);
+    return encode_host_core(c, static_cast<const char *>(rows), stride, len, static_cast<char *>(parity),
+                            parity_stride, ncw, chunk);
 }
 
 int ezrs_decode_host(ezrs_codec *c, void *data, size_t data_stride, unsigned len, void *parity,
@@ -1028,23 +950,17 @@ int ezrs_decode_host(ezrs_codec *c, void *data, size_t data_stride, unsigned len
                      size_t pos_stride, void *corr, size_t corr_stride, size_t ncw, size_t chunk) {
     if (!c) return -EINVAL;
     if (ncw == 0) return 0;
-    if (!data || !result) return -EINVAL;
-    const unsigned w = c->dev.mm <= 8 ? 1 : 2, NR = c->dev.nroots;
-    if (len < 1 || len > c->dev.load) return -EINVAL;
-    if (!parity) {
-        parity = static_cast<char *>(data) + (size_t)len * w;
-        parity_stride = data_stride;
-    }
-    if (ncw > 1 && (data_stride < len || parity_stride < NR)) return -EINVAL;
-    if (neras && !eras) return -EINVAL;
-    if (positions && ncw > 1 && pos_stride < NR) return -EINVAL;
-    if (corr && ncw > 1 && corr_stride < NR) return -EINVAL;
+    if (int r = check_rows(c, data, data_stride, len, parity, parity_stride, ncw, true)) return r;
+    if (int r = check_decode_out(c, ncw, {eras, eras_stride, neras, result, positions, pos_stride, corr,
+                                          corr_stride}))
+        return r;
+    const unsigned w = sym_bytes(c->dev), NR = c->dev.nroots;
     // erasure columns to stage: the row stride (capped at NR); a single codeword may pass
     // eras_stride 0, and then carries neras[0] entries
     size_t ecols = eras ? (eras_stride < NR ? eras_stride : NR) : 0;
     if (eras && ncw == 1 && eras_stride == 0) ecols = neras ? (neras[0] < NR ? neras[0] : NR) : 0;
-    if (eras && ecols == 0 && ncw > 1) return -EINVAL;
     if (eras && ecols == 0) eras = nullptr, neras = nullptr;
+    const DecodeOut out{eras, eras_stride, neras, result, positions, pos_stride, corr, corr_stride};
     const bool inline_par = parity_stride == data_stride && data_stride >= (size_t)len + NR &&
                             static_cast<const char *>(parity) ==
                                 static_cast<const char *>(data) + (size_t)len * w;
@@ -1072,7 +988,7 @@ int ezrs_decode_host(ezrs_codec *c, void *data, size_t data_stride, unsigned len
         if (!pend[s].live) return 0;
         pend[s].live = false;
         HIP_TRY(hipStreamSynchronize(c->streams[s]));           // rows, indices, results, count
-        const char *hb = static_cast<const char *>(c->h_stage[s]);
+        const char *hb = static_cast<const char *>(c->h_stage.p[s]);
         const uint32_t *hix = reinterpret_cast<const uint32_t *>(hb + h_cp);
         const uint32_t cnt = *reinterpret_cast<const uint32_t *>(hb + h_cp + h_ix);
         const size_t k0 = pend[s].k0;
@@ -1094,52 +1010,53 @@ int ezrs_decode_host(ezrs_codec *c, void *data, size_t data_stride, unsigned len
         hipStream_t st = c->streams[s];
         const size_t n = ncw - k0 < chunk ? ncw - k0 : chunk;
         if (int r = finish(s)) return r;                        // chunk i-2 (this stream's buffers)
-        char *base = static_cast<char *>(c->d_stage[s]);
+        char *base = static_cast<char *>(c->d_stage.p[s]);
         char *dcw = base, *der = dcw + b_cw, *dne = der + b_er, *drs = dne + b_ne, *dps = drs + b_rs,
              *dco = dps + b_ps, *dsy = dco + b_co, *dct = dsy + b_sy;
-        char *hb = static_cast<char *>(c->h_stage[s]), *dhb = nullptr;
+        char *hb = static_cast<char *>(c->h_stage.p[s]), *dhb = nullptr;
         HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&dhb), hb, 0));
-        char *hd = static_cast<char *>(data) + k0 * data_stride * w;
-        char *hp = static_cast<char *>(parity) + k0 * parity_stride * w;
+        // the chunk as the caller holds it (h) and as it is staged on the device (d)
+        const size_t ds = row / w;
+        const DecodeArgs h = out.args(c, static_cast<char *>(data) + k0 * data_stride * w, data_stride, len,
+                                      static_cast<char *>(parity) + k0 * parity_stride * w, parity_stride,
+                                      k0, n);
+        const DecodeOut staged{eras ? reinterpret_cast<uint32_t *>(der) : nullptr, ecols,
+                               neras ? reinterpret_cast<uint32_t *>(dne) : nullptr,
+                               reinterpret_cast<int32_t *>(drs),
+                               positions ? reinterpret_cast<uint32_t *>(dps) : nullptr, NR,
+                               corr ? dco : nullptr, NR};
+        const DecodeArgs d = staged.args(c, dcw, ds, len, dcw + (size_t)len * w, ds, 0, n);
         const size_t span = ((n - 1) * data_stride + len + NR) * w;
         if (inline_par) {
-            HIP_TRY(hipMemcpyAsync(dcw, hd, span, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(dcw, h.data, span, hipMemcpyHostToDevice, st));
         } else {
-            HIP_TRY(ezrs::copy2d(dcw, row, hd, data_stride * w, (size_t)len * w, n,
+            HIP_TRY(ezrs::copy2d(dcw, row, h.data, data_stride * w, (size_t)len * w, n,
                                  hipMemcpyHostToDevice, st));
-            HIP_TRY(ezrs::copy2d(dcw + (size_t)len * w, row, hp, parity_stride * w,
-                                 (size_t)NR * w, n, hipMemcpyHostToDevice, st));
+            HIP_TRY(ezrs::copy2d(d.parity, row, h.parity, parity_stride * w, (size_t)NR * w, n,
+                                 hipMemcpyHostToDevice, st));
         }
         if (eras)
-            HIP_TRY(ezrs::copy2d(der, ecols * 4, eras + k0 * eras_stride, eras_stride * 4,
-                                 ecols * 4, n, hipMemcpyHostToDevice, st));
-        if (neras) HIP_TRY(hipMemcpyAsync(dne, neras + k0, n * 4, hipMemcpyHostToDevice, st));
+            HIP_TRY(ezrs::copy2d(der, ecols * 4, h.eras, eras_stride * 4, ecols * 4, n,
+                                 hipMemcpyHostToDevice, st));
+        if (neras) HIP_TRY(hipMemcpyAsync(dne, h.neras, n * 4, hipMemcpyHostToDevice, st));
         if (positions)
-            HIP_TRY(ezrs::copy2d(dps, (size_t)NR * 4, positions + k0 * pos_stride,
-                                 pos_stride * 4, (size_t)NR * 4, n, hipMemcpyHostToDevice, st));
+            HIP_TRY(ezrs::copy2d(dps, (size_t)NR * 4, h.positions, pos_stride * 4, (size_t)NR * 4, n,
+                                 hipMemcpyHostToDevice, st));
         if (corr)   // corr is copy-in/copy-out: entries the decode does not write keep their value
-            HIP_TRY(ezrs::copy2d(dco, (size_t)NR * w, static_cast<char *>(corr) + k0 * corr_stride * w,
-                                 corr_stride * w, (size_t)NR * w, n, hipMemcpyHostToDevice, st));
-        const size_t ds = row / w;
-        DecodeArgs a{dcw, ds, len, dcw + (size_t)len * w, ds,
-                     eras ? reinterpret_cast<uint32_t *>(der) : nullptr, ecols,
-                     neras ? reinterpret_cast<uint32_t *>(dne) : nullptr,
-                     reinterpret_cast<int32_t *>(drs),
-                     positions ? reinterpret_cast<uint32_t *>(dps) : nullptr, NR,
-                     corr ? dco : nullptr, NR, n};
-        HIP_TRY(dispatch_decode(c, a, reinterpret_cast<uint8_t *>(dsy), st));
+            HIP_TRY(ezrs::copy2d(dco, (size_t)NR * w, h.corr, corr_stride * w, (size_t)NR * w, n,
+                                 hipMemcpyHostToDevice, st));
+        HIP_TRY(dispatch_decode(c, d, reinterpret_cast<uint8_t *>(dsy), st));
         HIP_TRY(hipMemsetAsync(dct, 0, 4, st));
-        HIP_TRY(launch_compact_rows(reinterpret_cast<const int32_t *>(drs), n, dcw, row,
-                                    reinterpret_cast<uint32_t *>(dct), reinterpret_cast<uint32_t *>(dhb + h_cp),
-                                    dhb, pitch, st));
-        HIP_TRY(hipMemcpyAsync(result + k0, drs, n * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(launch_compact_rows(d.result, n, dcw, row, reinterpret_cast<uint32_t *>(dct),
+                                    reinterpret_cast<uint32_t *>(dhb + h_cp), dhb, pitch, st));
+        HIP_TRY(hipMemcpyAsync(h.result, drs, n * 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(hb + h_cp + h_ix, dct, 4, hipMemcpyDeviceToHost, st));
         if (positions)
-            HIP_TRY(ezrs::copy2d(positions + k0 * pos_stride, pos_stride * 4, dps,
-                                 (size_t)NR * 4, (size_t)NR * 4, n, hipMemcpyDeviceToHost, st));
+            HIP_TRY(ezrs::copy2d(h.positions, pos_stride * 4, dps, (size_t)NR * 4, (size_t)NR * 4, n,
+                                 hipMemcpyDeviceToHost, st));
         if (corr)
-            HIP_TRY(ezrs::copy2d(static_cast<char *>(corr) + k0 * corr_stride * w, corr_stride * w,
-                                 dco, (size_t)NR * w, (size_t)NR * w, n, hipMemcpyDeviceToHost, st));
+            HIP_TRY(ezrs::copy2d(h.corr, corr_stride * w, dco, (size_t)NR * w, (size_t)NR * w, n,
+                                 hipMemcpyDeviceToHost, st));
         pend[s] = {k0, true};
     }
     for (int s = 0; s < 2; ++s)

@@ -40,6 +40,9 @@ struct DevCodec {
     const uint8_t *from_dual;     // device, 256
 };
 
+// Bytes of the codec's datum (uint8_t symbols up to 8 bits, uint16_t above).
+inline unsigned sym_bytes(const DevCodec &d) { return d.mm <= 8 ? 1 : 2; }
+
 // Shard batches (ezrs_encode_shards / ezrs_decode_shards): codeword k is row j = k mod rows of
 // shard s = k / rows, at element offset s * pitch + j * stride; every row holds `len` data symbols
 // and its parity, except the shard's last row, which holds `tail` data symbols (a shortened

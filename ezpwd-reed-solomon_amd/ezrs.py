@@ -123,6 +123,7 @@ def lib():
         L.ezbch_decode_syn.argtypes = [_vp, _vp, _sz, _u, _vp, _vp, _sz, _sz, _vp]
         L.ezbch_encode_host.argtypes = [_vp, _vp, _sz, _u, _vp, _sz, _sz, _sz]
         L.ezbch_decode_host.argtypes = [_vp, _vp, _sz, _u, _vp, _sz, _vp, _vp, _sz, _sz, _sz]
+        L.ezbch_decode_syn_host.argtypes = [_vp, _vp, _sz, _u, _vp, _vp, _sz, _sz]
         _lib = L
     return _lib
 
@@ -151,15 +152,20 @@ def _dev_rows(t, what, device, itemsize, ndim=2):
     expected width; returns its row stride in elements (0 for None)."""
     if t is None:
         return 0
+    _dev_elems(t, what, device, itemsize)
+    if t.dim() != ndim or (ndim == 2 and t.shape[1] > 1 and t.stride(1) != 1):
+        raise EzrsError(f"{what}: expected a {ndim}-D tensor with contiguous rows")
+    return t.stride(0) if ndim == 2 else 1
+
+
+def _dev_elems(t, what, device, itemsize):
+    """A tensor on the codec's device with elements of the expected width, whatever its shape."""
     if not getattr(t, "is_cuda", False):
         raise EzrsError(f"{what}: expected a GPU tensor")
     if t.device.index != device:
         raise EzrsError(f"{what}: tensor on cuda:{t.device.index}, codec on cuda:{device}")
     if t.element_size() != itemsize:
         raise EzrsError(f"{what}: expected {itemsize}-byte elements, got {t.dtype}")
-    if t.dim() != ndim or (ndim == 2 and t.shape[1] > 1 and t.stride(1) != 1):
-        raise EzrsError(f"{what}: expected a {ndim}-D tensor with contiguous rows")
-    return t.stride(0) if ndim == 2 else 1
 
 
 def _host_rows(a, what, itemsize, ndim=2):
@@ -265,6 +271,29 @@ class Codec:
     def workspace_bytes(self, ncw):
         return int(lib().ezrs_workspace_bytes(self._h, ncw))
 
+    def _decode_out(self, ncw, eras, neras, result, positions, corr, like=None):
+        """The decode outputs of ncw codewords, validated: device tensors on the device of the
+        tensor `like`, or (like is None: the host forms) numpy arrays.  Allocates `result` when it
+        is None.  Returns result and the eight arguments eras .. corr_stride of the C call."""
+        w = self.info.datum_bytes
+        if like is None:
+            rows, ptr = _host_rows, _np
+            if result is None:
+                result = np.zeros(ncw, np.int32)
+        else:
+            def rows(t, what, itemsize, ndim=2):
+                return _dev_rows(t, what, self.device, itemsize, ndim)
+            ptr = _tp
+        es = rows(eras, "eras", 4)
+        rows(neras, "neras", 4, ndim=1)
+        qs = rows(positions, "positions", 4)
+        cs = rows(corr, "corr", w)
+        if result is None:
+            import torch
+            result = torch.empty(ncw, dtype=torch.int32, device=like.device)
+        rows(result, "result", 4, ndim=1)
+        return result, (ptr(eras), es, ptr(neras), ptr(result), ptr(positions), qs, ptr(corr), cs)
+
     # -- device batch forms ------------------------------------------------------------------
     def encode(self, data, length=None, parity=None, stream=None):
         """data: [ncw, stride] device tensor; parity: [ncw, >=nroots] tensor, or None: each row
@@ -284,23 +313,14 @@ class Codec:
     def decode(self, data, length=None, parity=None, eras=None, neras=None, result=None,
                positions=None, corr=None, stream=None):
         """In-place batch decode; returns the int32 result tensor."""
-        import torch
         w = self.info.datum_bytes
         ncw = data.shape[0]
         ds = _dev_rows(data, "data", self.device, w)
         ps = _dev_rows(parity, "parity", self.device, w)
-        es = _dev_rows(eras, "eras", self.device, 4)
-        _dev_rows(neras, "neras", self.device, 4, ndim=1)
-        qs = _dev_rows(positions, "positions", self.device, 4)
-        cs = _dev_rows(corr, "corr", self.device, w)
+        result, out = self._decode_out(ncw, eras, neras, result, positions, corr, like=data)
         length = data.shape[1] - self.nroots if length is None else length
-        if result is None:
-            result = torch.empty(ncw, dtype=torch.int32, device=data.device)
-        _dev_rows(result, "result", self.device, 4, ndim=1)
-        _check(lib().ezrs_decode(
-            self._h, _tp(data), ds, length, _tp(parity), ps, _tp(eras), es, _tp(neras),
-            _tp(result), _tp(positions), qs, _tp(corr), cs, ncw, _stream_ptr(stream)),
-            "ezrs_decode")
+        _check(lib().ezrs_decode(self._h, _tp(data), ds, length, _tp(parity), ps, *out, ncw,
+                                 _stream_ptr(stream)), "ezrs_decode")
         return result
 
     # -- shard batches (rsencode layout per shard) --------------------------------------------
@@ -324,34 +344,19 @@ class Codec:
                       positions=None, corr=None, stream=None):
         """In-place decode of every codeword of every shard; returns the int32 result tensor
         [nshards * codewords per shard] (shard-major)."""
-        import torch
-        w = self.info.datum_bytes
         chunk = chunk or self.load
-        sp = _dev_rows(shards, "shards", self.device, w)
-        es = _dev_rows(eras, "eras", self.device, 4)
-        _dev_rows(neras, "neras", self.device, 4, ndim=1)
-        qs = _dev_rows(positions, "positions", self.device, 4)
-        cs = _dev_rows(corr, "corr", self.device, w)
+        sp = _dev_rows(shards, "shards", self.device, self.info.datum_bytes)
         ncw = shards.shape[0] * self.shard_codewords(shard_len, chunk)
-        if result is None:
-            result = torch.empty(ncw, dtype=torch.int32, device=shards.device)
-        _dev_rows(result, "result", self.device, 4, ndim=1)
-        _check(lib().ezrs_decode_shards(
-            self._h, _tp(shards), sp, shard_len, chunk, shards.shape[0], _tp(eras), es, _tp(neras),
-            _tp(result), _tp(positions), qs, _tp(corr), cs, _stream_ptr(stream)), "ezrs_decode_shards")
+        result, out = self._decode_out(ncw, eras, neras, result, positions, corr, like=shards)
+        _check(lib().ezrs_decode_shards(self._h, _tp(shards), sp, shard_len, chunk, shards.shape[0], *out,
+                                        _stream_ptr(stream)), "ezrs_decode_shards")
         return result
 
     # -- interleaved frames (CCSDS depth I, striped shards) ------------------------------------
     def _frames(self, frames):
         """Validate a [nframes, len + nroots, depth] device tensor with a contiguous last
         dimension; returns (frame_pitch, sym_stride, depth, len, nframes)."""
-        w = self.info.datum_bytes
-        if not getattr(frames, "is_cuda", False):
-            raise EzrsError("frames: expected a GPU tensor")
-        if frames.device.index != self.device:
-            raise EzrsError(f"frames: tensor on cuda:{frames.device.index}, codec on cuda:{self.device}")
-        if frames.element_size() != w:
-            raise EzrsError(f"frames: expected {w}-byte elements, got {frames.dtype}")
+        _dev_elems(frames, "frames", self.device, self.info.datum_bytes)
         if frames.dim() != 3 or (frames.shape[2] > 1 and frames.stride(2) != 1):
             raise EzrsError("frames: expected a 3-D tensor [nframes, len + nroots, depth] with a "
                             "contiguous last dimension")
@@ -376,20 +381,10 @@ class Codec:
                            corr=None, stream=None):
         """In-place decode of every codeword of every frame; returns the int32 result tensor
         [nframes * depth] (frame-major, k = f * depth + j) -- ezrs_decode_interleaved."""
-        import torch
-        w = self.info.datum_bytes
         fp, ss, depth, length, nframes = self._frames(frames)
-        es = _dev_rows(eras, "eras", self.device, 4)
-        _dev_rows(neras, "neras", self.device, 4, ndim=1)
-        qs = _dev_rows(positions, "positions", self.device, 4)
-        cs = _dev_rows(corr, "corr", self.device, w)
-        if result is None:
-            result = torch.empty(nframes * depth, dtype=torch.int32, device=frames.device)
-        _dev_rows(result, "result", self.device, 4, ndim=1)
-        _check(lib().ezrs_decode_interleaved(
-            self._h, _tp(frames), fp, ss, depth, length, nframes, _tp(eras), es, _tp(neras),
-            _tp(result), _tp(positions), qs, _tp(corr), cs, _stream_ptr(stream)),
-            "ezrs_decode_interleaved")
+        result, out = self._decode_out(nframes * depth, eras, neras, result, positions, corr, like=frames)
+        _check(lib().ezrs_decode_interleaved(self._h, _tp(frames), fp, ss, depth, length, nframes, *out,
+                                             _stream_ptr(stream)), "ezrs_decode_interleaved")
         return result
 
     def recon_plan(self, length, lost):
@@ -420,17 +415,11 @@ class Codec:
         ncw = data.shape[0]
         ds = _host_rows(data, "data", w)
         ps = _host_rows(parity, "parity", w)
-        es = _host_rows(eras, "eras", 4)
-        _host_rows(neras, "neras", 4, ndim=1)
-        qs = _host_rows(positions, "positions", 4)
-        cs = _host_rows(corr, "corr", w)
+        result, out = self._decode_out(ncw, eras, neras, None, positions, corr)
         length = data.shape[1] - self.nroots if length is None else length
-        result = np.zeros(ncw, np.int32)
-        _check(lib().ezrs_decode_host(
-            self._h, _np(data), ds, length, _np(parity), ps, _np(eras), es, _np(neras),
-            _np(result), _np(positions), qs, _np(corr), cs, ncw, chunk), "ezrs_decode_host")
+        _check(lib().ezrs_decode_host(self._h, _np(data), ds, length, _np(parity), ps, *out, ncw, chunk),
+               "ezrs_decode_host")
         return result
-
 
     # -- rsencode wire format -------------------------------------------------------------------
     def stream_encode(self, data, chunk=128):
