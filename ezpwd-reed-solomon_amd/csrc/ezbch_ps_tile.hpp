@@ -155,15 +155,21 @@ __device__ __forceinline__ void tile_loop(const BpsArgs &a, uint8_t *lds, Fin &&
         if constexpr (NV >= 0) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NV) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         const uint32_t toff = tile * tb;
-        if (w == 0 && toff + tb >= a.span) {
-            // a 16-byte DMA piece that crosses the span's end comes back all-zero: re-read the last
-            // 64 bytes one by one (out-of-range bytes read as zero)
-            const uint32_t off = a.span - 64u + l;
-            uint32_t v;
-            asm volatile("buffer_load_ubyte %0, %1, %2, 0 offen\n\ts_waitcnt vmcnt(0)"
-                         : "=&v"(v) : "v"(off), "s"(rsrc) : "memory");
-            if (off >= toff && off < a.span)
-                asm volatile("ds_write_b8 %0, %1\n\ts_waitcnt lgkmcnt(0)" :: "v"(img + (off - toff)), "v"(v) : "memory");
+        if (toff + tb >= a.span) {                         // the launch's last tile (workgroup-uniform)
+            // the part of a 16-byte DMA piece that crosses the span's end comes back zero (the
+            // dword that crosses it; at worst the whole piece): re-read the last 64 bytes one by
+            // one (out-of-range bytes read as zero).  That piece is wave (ndma - 1) % TW's: only
+            // once every wave's share has landed (the barrier) may wave 0 write over it, or the
+            // zeros could land after the bytes (as k_pq_lin and k_pt_lin)
+            asm volatile("s_barrier" ::: "memory");
+            if (w == 0) {
+                const uint32_t off = a.span - 64u + l;
+                uint32_t v;
+                asm volatile("buffer_load_ubyte %0, %1, %2, 0 offen\n\ts_waitcnt vmcnt(0)"
+                             : "=&v"(v) : "v"(off), "s"(rsrc) : "memory");
+                if (off >= toff && off < a.span)
+                    asm volatile("ds_write_b8 %0, %1\n\ts_waitcnt lgkmcnt(0)" :: "v"(img + (off - toff)), "v"(v) : "memory");
+            }
         }
         // all shares of the image are in, and every wave is done with the other image and the
         // exchange words

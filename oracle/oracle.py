@@ -366,7 +366,9 @@ def _bch_lib():
 
 class BCH:
     """BCH codec in the restatement: BCH(m, t, prim_poly=0), i.e. ezpwd::bch_base(m, t, prim_poly)
-    (c++/ezpwd/bch:54-61).  Parity status: pinned by the reference's BCH fixtures only."""
+    (c++/ezpwd/bch:54-61).  Parity status: pinned by the reference's BCH fixtures at
+    BCH(255,239,2), and to first principles (tests/bch_first_principles.py) for every codec of
+    tests/test_bch_gpu.py."""
 
     def __init__(self, m, t, poly=0):
         L = _bch_lib()
