@@ -59,6 +59,14 @@ struct ezrs_recon {
     uint32_t *d_tab = nullptr;    // recon_table
 };
 
+// A parity-update plan: one set of changed data positions of one codec and length; const after
+// ezrs_update_create.
+struct ezrs_update {
+    int device = 0;
+    unsigned mm = 0, nroots = 0, len = 0, nchg = 0;
+    uint32_t *d_tab = nullptr;    // recon_table with survivors = changed, lost = the parity positions
+};
+
 namespace {
 
 constexpr size_t kReconMaxTable = (size_t)64 << 20;   // bytes of a plan's device table (engine limit)
@@ -750,6 +758,103 @@ int ezrs_reconstruct_interleaved(const ezrs_recon *p, void *frames, size_t frame
                 recon_row_pad(p->nroots), result ? p->nroots : p->nlost};
     hipError_t e = launch_recon(a, nframes, p->d_tab, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return hip_fail(e, "reconstruction launch");
+    return 0;
+}
+
+// ---- in-place parity update -----------------------------------------------------------------------
+int ezrs_update_create(ezrs_update **out, const ezrs_codec *c, unsigned len, const uint32_t *changed,
+                       unsigned nchanged) {
+    if (!out) return -EINVAL;
+    *out = nullptr;
+    if (!c || !changed) return -EINVAL;
+    const CodecMath &m = c->math;
+    if (!update_check(m, len, changed, nchanged)) {
+        g_last_error = "update plan: len outside 1..load, or changed positions that are not 1..len "
+                       "distinct positions below len";
+        return -EINVAL;
+    }
+    const unsigned NR = m.spec.nroots;
+    const size_t words = recon_table_words(m.spec.mm, NR, nchanged, NR);
+    if (words * sizeof(uint32_t) > kReconMaxTable) {
+        g_last_error = "update plan: device table above 64 MiB";
+        return -ENOTSUP;
+    }
+    ezrs_update *p = nullptr;
+    std::vector<uint32_t> tab;
+    try {
+        p = new ezrs_update;
+        std::vector<uint16_t> cols;
+        if (!update_build(m, len, changed, nchanged, cols)) {
+            delete p;
+            return -EINVAL;
+        }
+        std::vector<uint32_t> par(NR);
+        for (unsigned i = 0; i < NR; ++i) par[i] = len + i;
+        recon_table(m.spec.mm, NR, cols, std::vector<uint32_t>(changed, changed + nchanged), par.data(), NR, tab);
+    } catch (const std::bad_alloc &) {
+        delete p;
+        return -ENOMEM;
+    }
+    p->device = c->device;
+    p->mm = m.spec.mm;
+    p->nroots = NR;
+    p->len = len;
+    p->nchg = nchanged;
+    DeviceGuard g(c->device);
+    hipError_t e;
+    if ((e = hipMalloc(&p->d_tab, tab.size() * sizeof(uint32_t))) != hipSuccess ||
+        (e = hipMemcpy(p->d_tab, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice)) !=
+            hipSuccess) {
+        ezrs_update_destroy(p);
+        return hip_fail(e, "hipMalloc(update table)");
+    }
+    *out = p;
+    return 0;
+}
+
+int ezrs_update_destroy(ezrs_update *p) {
+    if (!p) return 0;
+    DeviceGuard g(p->device);
+    if (p->d_tab) (void)hipFree(p->d_tab);
+    delete p;
+    return 0;
+}
+
+int ezrs_update_interleaved(const ezrs_update *p, void *frames, size_t frame_pitch, size_t sym_stride,
+                            size_t depth, size_t nframes, const void *newsyms, size_t new_frame_pitch,
+                            size_t new_sym_stride, void *stream) {
+    if (!p) return -EINVAL;
+    if (nframes == 0) return 0;
+    if (!frames || !newsyms || depth == 0 || sym_stride < depth || new_sym_stride < depth) return -EINVAL;
+    const size_t ns = (size_t)p->len + p->nroots;
+    if (nframes > 1 && (frame_pitch < (ns - 1) * sym_stride + depth ||
+                        new_frame_pitch < (size_t)(p->nchg - 1) * new_sym_stride + depth))
+        return -EINVAL;
+    if (depth > SIZE_MAX / nframes) return -EINVAL;
+    if (nframes == 1) frame_pitch = new_frame_pitch = 0;   // one frame: the pitches are not used
+    DeviceGuard g(p->device);
+    UpdateArgs a{frames, frame_pitch, sym_stride, depth, 0, 0, 0, 0, newsyms, new_frame_pitch, new_sym_stride,
+                 p->nchg, p->len, p->nroots, p->mm, recon_row_pad(p->nroots)};
+    hipError_t e = launch_update(a, nframes, p->d_tab, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "update launch");
+    return 0;
+}
+
+int ezrs_update_bitmatrix(unsigned symbol_bits, unsigned poly, unsigned fcr, unsigned prim, unsigned nroots,
+                          int dual, unsigned len, const uint32_t *changed, unsigned nchanged, uint16_t *cols,
+                          size_t cols_cap) {
+    if (!cols || !changed) return -EINVAL;
+    CodecMath m;
+    if (!m.build(CodecSpec{symbol_bits, poly, fcr, prim, nroots, dual ? 1 : 0})) return -EINVAL;
+    if (!update_check(m, len, changed, nchanged)) return -EINVAL;
+    if (cols_cap < (size_t)nroots * nchanged * symbol_bits) return -EINVAL;
+    try {
+        std::vector<uint16_t> c;
+        if (!update_build(m, len, changed, nchanged, c)) return -EINVAL;
+        std::copy(c.begin(), c.end(), cols);
+    } catch (const std::bad_alloc &) {
+        return -ENOMEM;
+    }
     return 0;
 }
 

@@ -223,4 +223,26 @@ struct ReconArgs {
 };
 hipError_t launch_recon(const ReconArgs &a, size_t nframes, const uint32_t *tab, hipStream_t s);
 
+// In-place parity update of interleaved frames (ezrs_recon.hip; ezrs_update_create /
+// ezrs_update_interleaved): the code is linear, so parity_new = parity_old ^ G[:, changed] *
+// (data_new ^ data_old), G the rebuild rows of the all-parity reconstruction plan (recon_build with
+// lost = len .. len + NROOTS - 1).  update_check: len in 1..load and nchanged (1..len) distinct
+// positions below len.  update_build: the columns `changed` of G, cols[row][r][bit]; false where
+// update_check fails.  The device table is recon_table with survivors = changed and lost = the
+// parity positions.
+bool update_check(const CodecMath &m, unsigned len, const uint32_t *changed, unsigned nchanged);
+bool update_build(const CodecMath &m, unsigned len, const uint32_t *changed, unsigned nchanged,
+                  std::vector<uint16_t> &cols);
+struct UpdateArgs {
+    void *frames;
+    size_t frame_pitch, sym_stride, depth;
+    size_t j0, runs;              // set per launch: first codeword of a frame, lanes per frame
+    size_t f0, nf;                // set per launch: frames
+    const void *newsyms;          // [frame][changed position][codeword]
+    size_t new_frame_pitch, new_sym_stride;
+    unsigned nchg, len, nroots, mm;
+    unsigned nrp;                 // recon_row_pad(nroots)
+};
+hipError_t launch_update(const UpdateArgs &a, size_t nframes, const uint32_t *tab, hipStream_t s);
+
 } // namespace ezrs

@@ -31,6 +31,10 @@
 // are taken RB at a time (RB accumulators per dword of the run); the blocks of a plan with more
 // rows are looped inside the kernel, so the check rows of all blocks are OR-ed in registers and
 // `result` is written once, whatever the order.
+//
+// The in-place parity update (ezrs_update_create / ezrs_update_interleaved, k_update) is the same
+// machinery on the difference of a few data symbols: the columns of the all-parity matrix at the
+// changed positions, applied to new ^ old and XOR-ed into the parity where it lies.
 #include <algorithm>
 #include <cerrno>
 #include <new>
@@ -186,6 +190,33 @@ void recon_table(unsigned mm, unsigned nroots, const std::vector<uint16_t> &cols
     uint32_t *fix = tail + nsurv + nlost;           // see apply()
     for (size_t i = 0; i < (size_t)nsurv * mm; ++i)
         for (unsigned r = 0; r < nrp; ++r) fix[r] ^= tab[i * nrp + r] & 0x7fff7fffu;
+}
+
+bool update_check(const CodecMath &m, unsigned len, const uint32_t *changed, unsigned nchanged) {
+    if (len < 1 || len > m.load || !changed || nchanged < 1 || nchanged > len) return false;
+    std::vector<uint8_t> seen(len, 0);
+    for (unsigned r = 0; r < nchanged; ++r) {
+        if (changed[r] >= len || seen[changed[r]]) return false;
+        seen[changed[r]] = 1;
+    }
+    return true;
+}
+
+// The all-parity plan's survivors are the data positions 0 .. len - 1 in order, so survivor column
+// c of its matrix is data position c.
+bool update_build(const CodecMath &m, unsigned len, const uint32_t *changed, unsigned nchanged,
+                  std::vector<uint16_t> &cols) {
+    if (!update_check(m, len, changed, nchanged)) return false;
+    const unsigned NR = m.spec.nroots, mm = m.spec.mm;
+    std::vector<uint32_t> par(NR), surv;
+    for (unsigned i = 0; i < NR; ++i) par[i] = len + i;
+    std::vector<uint16_t> all;
+    if (!recon_build(m, len, par.data(), NR, all, surv)) return false;
+    cols.resize((size_t)NR * nchanged * mm);
+    for (unsigned i = 0; i < NR; ++i)
+        for (unsigned r = 0; r < nchanged; ++r)
+            std::copy_n(&all[((size_t)i * len + changed[r]) * mm], mm, &cols[((size_t)i * nchanged + r) * mm]);
+    return true;
 }
 
 namespace recon {
@@ -489,11 +520,265 @@ static hipError_t launch(ReconArgs a, size_t nframes, const uint32_t *tab, hipSt
     return e;
 }
 
+// ---- in-place parity update (ezrs_update_interleaved) ---------------------------------------------
+// The delta form: parity ^= G[:, changed] * (new ^ old).  The plan table is recon_table with the
+// changed positions as the survivors, so the deltas go through apply / apply8 / apply8x2 like
+// survivors do.  Where the registers allow it the accumulators start as the old parity instead of
+// zero, which puts the parity loads in flight with the data loads; else the old parity is read
+// where it is stored.  Either way its bits above the symbol stay as they were (the columns are
+// symbols, and so is `fix`).
+
+// N changed positions from c0: the old and the new symbols, loaded together; d = old ^ new.
+template <typename T, int V, int N>
+__device__ __forceinline__ void udelta(const UpdateArgs &a, const T *base, const T *nbase,
+                                       const uint32_t *__restrict__ chg, unsigned c0,
+                                       uint32_t (&d)[N][Run<T, V>::ND], uint32_t (&nw)[N][Run<T, V>::ND]) {
+    using R = Run<T, V>;
+#pragma unroll
+    for (int u = 0; u < N; ++u) {
+        R::load(base + (size_t)chg[c0 + u] * a.sym_stride, d[u]);
+        R::load(nbase + (size_t)(c0 + u) * a.new_sym_stride, nw[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < N; ++u)
+#pragma unroll
+        for (int i = 0; i < R::ND; ++i) d[u][i] ^= nw[u][i];
+}
+
+// The N deltas of the positions from c0 into the accumulators of a row block; K: the coefficients,
+// already at the block's first row.  m = 8 takes them in pairs.
+template <typename T, int RB, int V, int MB, int N>
+__device__ __forceinline__ void ufeed(const UpdateArgs &a, const uint32_t *__restrict__ K, unsigned c0,
+                                      const uint32_t (&d)[N][Run<T, V>::ND],
+                                      uint32_t (&acc)[RB][Run<T, V>::ND]) {
+    constexpr int ND = Run<T, V>::ND;
+    constexpr bool BYTES = sizeof(T) == 1;
+    const unsigned mm = MB ? MB : a.mm;
+    const size_t kstep = BYTES ? (size_t)((mm + 2) / 3) * 2 * a.nrp : (size_t)mm * a.nrp;
+    auto one = [&](const uint32_t (&x)[ND], unsigned c) {
+        if constexpr (BYTES) apply8<RB, ND, MB>(x, K + c * kstep, a.nrp, mm, acc);
+        else apply<RB, ND, MB>(x, K + c * kstep, a.nrp, mm, 0x00010001u, 0x7fff7fffu, acc);
+    };
+    if constexpr (BYTES && MB == 8) {
+#pragma unroll
+        for (int u = 0; u + 1 < N; u += 2)
+            apply8x2<RB, ND>(d[u], d[u + 1], K + (c0 + u) * kstep, K + (c0 + u + 1) * kstep, a.nrp, acc);
+        if constexpr (N & 1) one(d[N - 1], c0 + N - 1);
+    } else {
+#pragma unroll
+        for (int u = 0; u < N; ++u) one(d[u], c0 + u);
+    }
+}
+
+// By the accumulator registers of a row block (RB x dwords of the run), what keeps every
+// instantiation clear of spills and all but the two largest at four or more waves per SIMD
+// (resource report in DESIGN section 4): whether the old parity is loaded ahead of the arithmetic
+// (else it is read where it is stored), how many changed positions' loads (old and new) are issued
+// together, and at most how many deltas stay in registers.
+constexpr bool uearly(int accs) { return accs < 64; }
+constexpr int ugroup(int accs) { return accs >= 128 ? 2 : (int)kUnroll; }
+constexpr unsigned ukeep(int accs) { return accs >= 128 ? 1 : accs >= 64 ? 2 : kUnroll; }
+
+// One row block.  NC != 0: the plan's NC deltas are in d.  NC == 0: all changed positions are read
+// (again), a group's loads issued together, the ragged end one by one.
+template <typename T, int RB, int V, int MB, int NC>
+__device__ __forceinline__ void usweep(const UpdateArgs &a, const T *base, const T *nbase,
+                                       const uint32_t *__restrict__ chg, const uint32_t *__restrict__ K,
+                                       const uint32_t (&d)[NC ? NC : 1][Run<T, V>::ND],
+                                       uint32_t (&acc)[RB][Run<T, V>::ND]) {
+    constexpr int ND = Run<T, V>::ND, G = ugroup(RB * ND);
+    if constexpr (NC != 0) {
+        ufeed<T, RB, V, MB, NC>(a, K, 0, d, acc);
+    } else {
+        unsigned c = 0;
+        for (; c + G <= a.nchg; c += G) {
+            uint32_t e[G][ND], w[G][ND];
+            udelta<T, V, G>(a, base, nbase, chg, c, e, w);
+            ufeed<T, RB, V, MB, G>(a, K, c, e, acc);
+        }
+        for (; c < a.nchg; ++c) {
+            uint32_t e[1][ND], w[1][ND];
+            udelta<T, V, 1>(a, base, nbase, chg, c, e, w);
+            ufeed<T, RB, V, MB, 1>(a, K, c, e, acc);
+        }
+    }
+}
+
+// A lane's codewords through every row block.  NC = 1 .. kUnroll changed positions of a plan of one
+// row block: the new symbols stay in registers from the delta to the write-back.  NC = 0, any plan:
+// every block reads old and new again (mostly from L2), and the new symbols once more at the end.
+// (Deltas kept across several blocks are not built: the compiler then hoists every bit mask and
+// selector of every delta out of the block loop and the kernels need 160 - 256 VGPRs.)  Either way
+// the data is overwritten only after the last block.
+template <typename T, int RB, int V, int NC>
+__device__ __forceinline__ void ubody(const UpdateArgs &a, const uint32_t *__restrict__ K,
+                                      const uint32_t *__restrict__ chg, const uint32_t *__restrict__ fix,
+                                      T *base, const T *nbase) {
+    using R = Run<T, V>;
+    constexpr int ND = R::ND;
+    T *const par = base + (size_t)a.len * a.sym_stride;
+    uint32_t d[NC ? NC : 1][ND], nw[NC ? NC : 1][ND];
+    if constexpr (NC != 0) udelta<T, V, NC>(a, base, nbase, chg, 0, d, nw);
+    auto block = [&](unsigned r0) {
+        uint32_t acc[RB][ND];
+        if constexpr (uearly(RB * ND)) {
+            // The accumulators start as the old parity, whose loads are so in flight with the data
+            // loads.  The rows of a last block's padding start as the last parity row once more (no
+            // load leaves the stripe, and no control flow on the way to the arithmetic); they are
+            // never stored.
+#pragma unroll
+            for (int r = 0; r < RB; ++r) {
+                const unsigned row = r0 + r < a.nroots ? r0 + r : a.nroots - 1;
+                R::load(par + (size_t)row * a.sym_stride, acc[r]);
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < RB; ++r)
+#pragma unroll
+                for (int i = 0; i < ND; ++i) acc[r][i] = 0;
+        }
+        const uint32_t *const Kb = K + (sizeof(T) == 1 ? 2 * r0 : r0);
+        if (a.mm == 8) usweep<T, RB, V, 8, NC>(a, base, nbase, chg, Kb, d, acc);
+        else usweep<T, RB, V, 0, NC>(a, base, nbase, chg, Kb, d, acc);
+#pragma unroll
+        for (int r = 0; r < RB; ++r)
+            if (r0 + r < a.nroots) {
+                T *const p = par + (size_t)(r0 + r) * a.sym_stride;
+                const uint32_t fx = fix[r0 + r];
+                if constexpr (uearly(RB * ND)) {
+#pragma unroll
+                    for (int i = 0; i < ND; ++i) acc[r][i] ^= fx;
+                } else {
+                    uint32_t old[ND];
+                    R::load(p, old);
+#pragma unroll
+                    for (int i = 0; i < ND; ++i) acc[r][i] ^= fx ^ old[i];
+                }
+                R::store(p, acc[r]);
+            }
+    };
+    if constexpr (NC != 0) {
+        block(0);
+#pragma unroll
+        for (int u = 0; u < NC; ++u) R::store(base + (size_t)chg[u] * a.sym_stride, nw[u]);
+    } else {
+        for (unsigned r0 = 0; r0 < a.nroots; r0 += RB) block(r0);
+        for (unsigned c = 0; c < a.nchg; ++c) {
+            uint32_t x[ND];
+            R::load(nbase + (size_t)c * a.new_sym_stride, x);
+            R::store(base + (size_t)chg[c] * a.sym_stride, x);
+        }
+    }
+}
+
+// K: the coefficients of the changed positions; chg: the positions; fix: [nrp] (recon_table).
+template <typename T, int RB, int V>
+__global__ void __launch_bounds__(256) k_update(UpdateArgs a, const uint32_t *__restrict__ K,
+                                                const uint32_t *__restrict__ chg,
+                                                const uint32_t *__restrict__ fix) {
+    using R = Run<T, V>;
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= a.runs * a.nf) return;
+    size_t f, q;
+    if (((t | a.runs) >> 32) == 0) {                // 32-bit division (see shard_row)
+        const uint32_t t32 = (uint32_t)t, r32 = (uint32_t)a.runs, f32 = t32 / r32;
+        f = f32;
+        q = t32 - f32 * r32;
+    } else {
+        f = t / a.runs;
+        q = t - f * a.runs;
+    }
+    const size_t j = a.j0 + q * R::EPL;
+    T *const base = static_cast<T *>(a.frames) + (a.f0 + f) * a.frame_pitch + j;
+    const T *const nbase = static_cast<const T *>(a.newsyms) + (a.f0 + f) * a.new_frame_pitch + j;
+    static_assert(kUnroll == 4, "one case per count of changed positions kept in registers");
+    constexpr unsigned KEEP = ukeep(RB * R::ND);
+    const unsigned nc = a.nroots <= RB && a.nchg <= KEEP ? a.nchg : 0;
+    if (nc == 1) {
+        ubody<T, RB, V, 1>(a, K, chg, fix, base, nbase);
+    } else if (nc == 2) {
+        if constexpr (KEEP >= 2) ubody<T, RB, V, 2>(a, K, chg, fix, base, nbase);
+    } else if (nc == 3) {
+        if constexpr (KEEP >= 4) ubody<T, RB, V, 3>(a, K, chg, fix, base, nbase);
+    } else if (nc == 4) {
+        if constexpr (KEEP >= 4) ubody<T, RB, V, 4>(a, K, chg, fix, base, nbase);
+    } else {
+        ubody<T, RB, V, 0>(a, K, chg, fix, base, nbase);
+    }
+}
+
+template <typename T, int V>
+static void ulaunch_rb(unsigned rb, dim3 grid, hipStream_t s, const UpdateArgs &a, const uint32_t *K,
+                       const uint32_t *chg, const uint32_t *fix) {
+    const dim3 block(256);
+    switch (rb) {
+    case 4: hipLaunchKernelGGL((k_update<T, 4, V>), grid, block, 0, s, a, K, chg, fix); break;
+    case 8: hipLaunchKernelGGL((k_update<T, 8, V>), grid, block, 0, s, a, K, chg, fix); break;
+    case 16: hipLaunchKernelGGL((k_update<T, 16, V>), grid, block, 0, s, a, K, chg, fix); break;
+    default:                                        // 32 rows: the bit-column form only (ulaunch())
+        if constexpr (sizeof(T) == 2) hipLaunchKernelGGL((k_update<T, 32, V>), grid, block, 0, s, a, K, chg, fix);
+        break;
+    }
+}
+
+// Codewords [j0, j0 + n) of every frame, as launch_span.
+template <typename T, int V>
+static hipError_t ulaunch_span(UpdateArgs a, unsigned rb, size_t j0, size_t n, size_t nframes,
+                               const uint32_t *tab, hipStream_t s) {
+    constexpr size_t EPL = Run<T, V>::EPL;
+    if (!n) return hipSuccess;
+    a.j0 = j0;
+    a.runs = n / EPL;
+    const size_t per = a.mm <= 8 ? (size_t)((a.mm + 2) / 3) * 2 : a.mm;   // recon_coef_words
+    const uint32_t *K = tab, *chg = tab + (size_t)a.nchg * per * a.nrp, *fix = chg + a.nchg + a.nroots;
+    const size_t maxt = (size_t)1 << 38;            // threads per launch (2^30 workgroups)
+    if (a.runs > maxt) return hipErrorInvalidValue;
+    const size_t fstep = maxt / a.runs;
+    for (size_t f0 = 0; f0 < nframes; f0 += fstep) {
+        a.f0 = f0;
+        a.nf = nframes - f0 < fstep ? nframes - f0 : fstep;
+        const dim3 grid((unsigned)((a.runs * a.nf + 255) / 256));
+        ulaunch_rb<T, V>(rb, grid, s, a, K, chg, fix);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+template <typename T>
+static hipError_t ulaunch(UpdateArgs a, size_t nframes, const uint32_t *tab, hipStream_t s) {
+    const unsigned cap = sizeof(T) == 1 ? 16 : 32;  // rows per block, as launch()
+    unsigned rb = 4;
+    while (rb < cap && rb < a.nroots) rb *= 2;
+    // widest access every symbol row of every frame is aligned for, in `frames` and in `newsyms`
+    const size_t w = sizeof(T);
+    size_t al = (size_t)(uintptr_t)a.frames | a.sym_stride * w | (size_t)(uintptr_t)a.newsyms |
+                a.new_sym_stride * w;
+    if (nframes > 1) al |= a.frame_pitch * w | a.new_frame_pitch * w;
+    const size_t e16 = 16 / w, e4 = 4 / w;
+    size_t done = 0;
+    hipError_t e = hipSuccess;
+    if ((al & 15) == 0 && a.depth >= e16) {
+        done = a.depth / e16 * e16;
+        e = ulaunch_span<T, 4>(a, rb, 0, done, nframes, tab, s);
+    } else if ((al & 3) == 0 && a.depth >= e4) {
+        done = a.depth / e4 * e4;
+        e = ulaunch_span<T, 1>(a, rb, 0, done, nframes, tab, s);
+    }
+    if (e == hipSuccess) e = ulaunch_span<T, 0>(a, rb, done, a.depth - done, nframes, tab, s);   // ragged end
+    return e;
+}
+
 } // namespace recon
 
 hipError_t launch_recon(const ReconArgs &a, size_t nframes, const uint32_t *tab, hipStream_t s) {
     if (!a.nrows || !nframes) return hipSuccess;
     return a.mm <= 8 ? recon::launch<uint8_t>(a, nframes, tab, s) : recon::launch<uint16_t>(a, nframes, tab, s);
+}
+
+hipError_t launch_update(const UpdateArgs &a, size_t nframes, const uint32_t *tab, hipStream_t s) {
+    if (!a.nchg || !nframes) return hipSuccess;
+    return a.mm <= 8 ? recon::ulaunch<uint8_t>(a, nframes, tab, s) : recon::ulaunch<uint16_t>(a, nframes, tab, s);
 }
 
 } // namespace ezrs

@@ -104,6 +104,10 @@ def lib():
         L.ezrs_recon_destroy.argtypes = [_vp]
         L.ezrs_reconstruct_interleaved.argtypes = [_vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp]
         L.ezrs_recon_bitmatrix.argtypes = [_u, _u, _u, _u, _u, _i, _u, _vp, _u, _vp, _sz, _vp]
+        L.ezrs_update_create.argtypes = [C.POINTER(_vp), _vp, _u, _vp, _u]
+        L.ezrs_update_destroy.argtypes = [_vp]
+        L.ezrs_update_interleaved.argtypes = [_vp, _vp, _sz, _sz, _sz, _sz, _vp, _sz, _sz, _vp]
+        L.ezrs_update_bitmatrix.argtypes = [_u, _u, _u, _u, _u, _i, _u, _vp, _u, _vp, _sz]
         L.ezrs_kernel_path.argtypes = [_vp]
         L.ezrs_set_launch_rows.argtypes = [_vp, _sz]
         L.ezrs_set_semantics.argtypes = [_vp, _i]
@@ -393,6 +397,12 @@ class Codec:
         every codeword -- ezrs_recon_create.  Returns a Recon."""
         return Recon(self, length, lost)
 
+    def update_plan(self, length, changed):
+        """Parity-update plan for codewords of `length` data symbols whose data symbols at the
+        positions `changed` (relative to the first data symbol) are replaced in every codeword --
+        ezrs_update_create.  Returns an Update."""
+        return Update(self, length, changed)
+
     # -- host batch forms ----------------------------------------------------------------------
     def encode_host(self, data, length=None, parity=None, chunk=0):
         """data: [ncw, stride] numpy rows (only read); parity: [ncw, >=nroots] array, or None:
@@ -506,6 +516,81 @@ class Recon:
             self._h, _tp(frames), frames.stride(0), frames.stride(1), depth, nframes, _tp(result),
             _stream_ptr(stream)), "ezrs_reconstruct_interleaved")
         return result
+
+
+class Update:
+    """A parity-update plan (ezrs_update_create): one set of changed data positions shared by every
+    codeword; ``apply`` XORs G[:, changed]·(new ^ old) into the parity of interleaved frames where it
+    lies and stores the new data symbols.  The plan keeps nothing of the codec it was made from.
+
+    * ``changed``   the changed data positions, in the order given (the order of ``newsyms``' rows)
+    * ``nchanged``  len(changed)"""
+
+    def __init__(self, codec, length, changed):
+        self.changed = [int(p) for p in changed]
+        self.nchanged = len(self.changed)
+        self.length, self.nroots, self.device = int(length), codec.nroots, codec.device
+        self._w = codec.info.datum_bytes
+        arr = (C.c_uint32 * max(self.nchanged, 1))(*self.changed)
+        h = _vp()
+        self._h = None
+        _check(lib().ezrs_update_create(C.byref(h), codec._h, self.length, arr, self.nchanged),
+               "ezrs_update_create")
+        self._h = h
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            try:
+                lib().ezrs_update_destroy(h)
+            except Exception:
+                pass
+            self._h = None
+
+    def _sym_rows(self, t, what, nsym, shape):
+        """Validate a [nframes, nsym, depth] device tensor with a contiguous last dimension."""
+        if not getattr(t, "is_cuda", False):
+            raise EzrsError(f"{what}: expected a GPU tensor")
+        if t.device.index != self.device:
+            raise EzrsError(f"{what}: tensor on cuda:{t.device.index}, plan on cuda:{self.device}")
+        if t.element_size() != self._w:
+            raise EzrsError(f"{what}: expected {self._w}-byte elements, got {t.dtype}")
+        if t.dim() != 3 or (t.shape[2] > 1 and t.stride(2) != 1):
+            raise EzrsError(f"{what}: expected a 3-D tensor {shape} with a contiguous last dimension")
+        if t.shape[1] != nsym or t.shape[2] == 0:
+            raise EzrsError(f"{what}: {t.shape[1]} symbols per codeword, the plan has {nsym}, and a "
+                            "depth of at least 1")
+
+    def apply(self, frames, newsyms, stream=None):
+        """frames: [nframes, length + nroots, depth] device tensor as in Codec.encode_interleaved;
+        newsyms: [nframes, nchanged, depth] device tensor, row r the new contents of the symbols at
+        changed[r] (only read; it must not overlap the changed and parity symbols of `frames`).  The
+        parity of every codeword follows the change and the changed symbols take their new values;
+        nothing else is written."""
+        self._sym_rows(frames, "frames", self.length + self.nroots, "[nframes, len + nroots, depth]")
+        self._sym_rows(newsyms, "newsyms", self.nchanged, "[nframes, nchanged, depth]")
+        nframes, _, depth = frames.shape
+        if newsyms.shape[0] != nframes or newsyms.shape[2] != depth:
+            raise EzrsError(f"newsyms: shape {tuple(newsyms.shape)}, expected "
+                            f"({nframes}, {self.nchanged}, {depth})")
+        _check(lib().ezrs_update_interleaved(
+            self._h, _tp(frames), frames.stride(0), frames.stride(1), depth, nframes, _tp(newsyms),
+            newsyms.stride(0), newsyms.stride(1), _stream_ptr(stream)), "ezrs_update_interleaved")
+
+
+def update_bitmatrix(params, length, changed):
+    """The matrix of a parity-update plan on the host (ezrs_update_bitmatrix; no device).  params:
+    (symbol_bits, poly, fcr, prim, nroots, dual).  Returns cols, a uint16 array
+    [nroots, nchanged, symbol_bits]: parity symbol `row` changes by the XOR of cols[row, r, b] over
+    the set bits b of new ^ old at changed[r]."""
+    mm, poly, fcr, prim, nroots, dual = params
+    changed = [int(p) for p in changed]
+    cols = np.zeros((nroots, len(changed), mm), np.uint16)
+    arr = (C.c_uint32 * max(len(changed), 1))(*changed)
+    _check(lib().ezrs_update_bitmatrix(mm, poly, fcr, prim, nroots, int(bool(dual)), length, arr,
+                                       len(changed), _np(cols), cols.size),
+           "ezrs_update_bitmatrix")
+    return cols
 
 
 def recon_bitmatrix(params, length, lost):

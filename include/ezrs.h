@@ -275,6 +275,56 @@ int ezrs_recon_bitmatrix(unsigned symbol_bits, unsigned poly, unsigned fcr, unsi
                          unsigned nroots, int dual, unsigned len, const uint32_t *lost,
                          unsigned nlost, uint16_t *cols, size_t cols_cap, uint32_t *survivors);
 
+/* In-place parity update of interleaved frames (device-resident): the small write.  One or a few
+ * data shards of a stripe change and the parity shards must follow.  The code is linear, so with G
+ * the parity rows of the all-parity reconstruction plan (lost = len..len+NROOTS-1),
+ *   parity_new = parity_old ^ G[:, changed] * (data_new ^ data_old):
+ * only the changed symbols and the parity are read and written, whatever `len` is (the reference
+ * has no such call: it replaces encode() of the whole codeword, rs_base:868-904).
+ *   plan     `changed`: nchanged (1..len) distinct HOST positions of data symbols, 0 <= changed[r] <
+ *            len, relative to the codeword's first data symbol under both semantics of the codec.
+ *            ezrs_update_create takes those columns of the all-parity matrix, uploads them to the
+ *            codec's device in the reconstruction plan's table format and may synchronise; the plan
+ *            copies what it needs, so it stays valid after ezrs_destroy(codec); it is const
+ *            afterwards and may be shared by threads and streams.  -EINVAL: null out, codec or
+ *            changed; len outside 1..load; nchanged == 0 or > len; a position >= len or given
+ *            twice; -ENOTSUP when the plan's device table would exceed 64 MiB (the limit and the
+ *            formula of ezrs_recon_create with nchanged for the survivors); -ENOMEM.
+ *   call     `frames`: geometry as in ezrs_*_interleaved above; every frame of the call shares the
+ *            plan's positions.  `newsyms` holds the new contents of the changed symbols only:
+ *            newsyms[f*new_frame_pitch + r*new_sym_stride + j] is the new value of symbol changed[r]
+ *            of codeword j of frame f (strides in elements of the datum).  Asynchronous; no
+ *            workspace; never allocates, never synchronises.  For every codeword, with d_r =
+ *            newsyms ^ the old symbol in `frames`, parity symbol i gets ^= sum_r G[i][changed[r]] *
+ *            d_r, and then the changed data symbols are overwritten with newsyms.  Only those
+ *            nchanged data symbols and the NROOTS parity symbols of each codeword are written in
+ *            `frames`, no other element; `newsyms` is only read.  Bits above the symbol do not
+ *            enter the parity, for old and new values alike; the data symbols are stored as given;
+ *            a parity symbol's bits above the symbol are left as they were.
+ *            The old parity is read, not recomputed: a stripe whose parity was wrong by e before
+ *            the call is wrong by the same e afterwards (verify with an nlost == 0 reconstruction
+ *            plan where that matters).  `newsyms` must not overlap the written elements of
+ *            `frames`; that is the caller's contract and is not checked.
+ * -EINVAL: null plan, frames or newsyms; depth == 0; sym_stride < depth or new_sym_stride < depth;
+ * nframes > 1 with frame_pitch < (len + NROOTS - 1)*sym_stride + depth or with new_frame_pitch <
+ * (nchanged - 1)*new_sym_stride + depth; depth > SIZE_MAX / nframes.  nframes == 0 returns 0 and
+ * touches nothing. */
+typedef struct ezrs_update ezrs_update;
+int ezrs_update_create(ezrs_update **out, const ezrs_codec *codec, unsigned len,
+                       const uint32_t *changed, unsigned nchanged);
+int ezrs_update_destroy(ezrs_update *plan);   /* NULL: 0 */
+int ezrs_update_interleaved(const ezrs_update *plan, void *frames, size_t frame_pitch,
+                            size_t sym_stride, size_t depth, size_t nframes, const void *newsyms,
+                            size_t new_frame_pitch, size_t new_sym_stride, void *stream);
+/* The plan's matrix on the host, from the codec parameters of ezrs_create (no device is touched).
+ * cols: NROOTS * nchanged * symbol_bits uint16 (cols_cap: entries available), [row][r][bit]: the
+ * image, in the stored representation, of bit `bit` of the difference at changed[r] in parity
+ * symbol `row`; entries mean what ezrs_recon_bitmatrix's mean.
+ * -EINVAL: invalid codec parameters, the plan rules above, null cols, cols_cap too small. */
+int ezrs_update_bitmatrix(unsigned symbol_bits, unsigned poly, unsigned fcr, unsigned prim,
+                          unsigned nroots, int dual, unsigned len, const uint32_t *changed,
+                          unsigned nchanged, uint16_t *cols, size_t cols_cap);
+
 /* Host-memory forms: the same contracts with HOST pointers.  The batch is streamed through the
  * device in chunks of `chunk` codewords (0 = library default) over two HIP streams with
  * asynchronous copies; pinned host memory (ezrs_host_alloc) gets full PCIe overlap.  Blocking:

@@ -1,0 +1,146 @@
+#!/usr/bin/env python3
+"""In-place parity update of a striped frame (Update.apply) against the two ways to re-encode the
+whole stripe: the all-parity reconstruction (Recon.reconstruct without result, the fastest
+re-encode the project has) and the staged Codec.encode_interleaved, on the same buffers.  Neither
+comparison shares a kernel with the update.
+
+    python tools/update_bench.py [--gib 1.0] [--out profiles/update/update_bench.json]
+
+One frame per shape: len + nroots shards of `depth` symbols, symbol stride = depth, sized so that
+the frame holds at least --gib GiB (well past the 256 MiB Infinity Cache); newsyms is a packed
+[nchanged, depth] buffer.  Device events; every call is warmed; the three calls alternate in the
+same process, `reps` repeats per figure sized so that each figure has at least 0.5 s of timed work;
+the figure is the median, the spread (max - min) / median.  Repeats of the update find the new
+symbols already in place (a zero delta), which changes nothing in what it loads, computes or
+stores.  GB/s counts the frame's bytes once; hbm_fraction counts the bytes the update must move
+(old and new changed symbols and the parity read, changed symbols and parity written) against
+8 TB/s."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "ezpwd-reed-solomon_amd"))
+
+import torch  # noqa: E402
+
+import ezrs  # noqa: E402
+
+REPS = 5
+HBM = 8e12
+
+SHAPES = [
+    # (name, codec, len, changed)
+    ("RS(255,251) len 10, 1 changed", lambda: ezrs.Codec.rs(255, 251), 10, [3]),
+    ("RS(255,252) len 17, 1 changed", lambda: ezrs.Codec.rs(255, 252), 17, [9]),
+    ("RS(255,223) len 223, 1 changed", lambda: ezrs.Codec.rs(255, 223), 223, [100]),
+    ("RS(255,223) len 223, 4 changed", lambda: ezrs.Codec.rs(255, 223), 223, [5, 100, 101, 222]),
+    ("RS_CCSDS(255,223) len 223, 1 changed", lambda: ezrs.Codec.ccsds(223, True), 223, [100]),
+    ("RS(1023,1007) len 100, 1 changed", lambda: ezrs.Codec.rs(1023, 1007), 100, [50]),
+]
+
+
+def timed(fn, iters):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / 1e3 / iters          # seconds per call
+
+
+def figure(fns):
+    """fns: name -> callable, timed alternately; returns name -> {median_s, spread, iters}."""
+    iters = {}
+    for n, f in fns.items():
+        f()
+        torch.cuda.synchronize()
+        t = timed(f, 2)
+        iters[n] = max(2, int(0.5 / REPS / t) + 1)
+    runs = {n: [] for n in fns}
+    for _ in range(REPS):
+        for n, f in fns.items():
+            runs[n].append(timed(f, iters[n]))
+    return {n: {"median_s": statistics.median(v), "spread": (max(v) - min(v)) / statistics.median(v),
+                "iters": iters[n]} for n, v in runs.items()}
+
+
+def rand_rows(rows, depth, w, mask, g):
+    """[rows, depth] random symbols of w bytes."""
+    dt = torch.uint8 if w == 1 else torch.int16     # 16-bit symbols as int16: the bits are what counts
+    out = torch.empty((rows, depth), dtype=dt, device="cuda")
+    for s in range(rows):
+        out[s] = torch.randint(0, mask + 1, (depth,), generator=g, device="cuda", dtype=torch.int32).to(dt)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gib", type=float, default=1.0)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "update", "update_bench.json"))
+    args = ap.parse_args()
+    torch.cuda.set_device(0)
+    out = {"gib": args.gib, "reps": REPS, "device": torch.cuda.get_device_name(0), "results": []}
+    for name, mk, length, changed in SHAPES:
+        c = mk()
+        w, NR, nchg = c.info.datum_bytes, c.nroots, len(changed)
+        S = length + NR
+        depth = (int(args.gib * (1 << 30)) // (S * w) + 1023) // 1024 * 1024
+        g = torch.Generator(device="cuda").manual_seed(1)
+        shards = torch.empty((S, depth), dtype=torch.uint8 if w == 1 else torch.int16, device="cuda")
+        shards[:length] = rand_rows(length, depth, w, c.nn, g)
+        frames = shards[None]
+        parity = list(range(length, S))
+        plan = c.update_plan(length, changed)
+        reenc = c.recon_plan(length, parity)
+        reenc.reconstruct(frames)                   # the first parity
+        newsyms = rand_rows(nchg, depth, w, c.nn, g)[None]
+        # each path once, checked against the others: the update's parity must be what both
+        # re-encodes write on the new data
+        old = shards[changed].clone()
+        plan.apply(frames, newsyms)
+        torch.cuda.synchronize()
+        assert torch.equal(shards[changed], newsyms[0]), name
+        good = shards[parity].clone()
+        for what, fn in (("reencode_recon", lambda: reenc.reconstruct(frames)),
+                         ("reencode_staged", lambda: c.encode_interleaved(frames))):
+            shards[parity] = 0x5A
+            fn()
+            torch.cuda.synchronize()
+            assert torch.equal(shards[parity], good), (name, what)
+        plan.apply(frames, old[None])               # and back: a nonzero delta once more
+        reenc.reconstruct(frames)
+        torch.cuda.synchronize()
+        fg = figure({"update": lambda: plan.apply(frames, newsyms),
+                     "reencode_recon": lambda: reenc.reconstruct(frames),
+                     "reencode_staged": lambda: c.encode_interleaved(frames)})
+        torch.cuda.synchronize()
+        assert torch.equal(shards[parity], good), name
+        fbytes = S * depth * w
+        moved = (3 * nchg + 2 * NR) * depth * w     # old + new read, new written; parity read + written
+        t_u, t_r, t_e = (fg[k]["median_s"] for k in ("update", "reencode_recon", "reencode_staged"))
+        rec = {"shape": name, "len": length, "nroots": NR, "nchanged": nchg, "depth": depth,
+               "frame_bytes": fbytes, "update_bytes_moved": moved,
+               "t_update_ms": t_u * 1e3, "t_reencode_recon_ms": t_r * 1e3, "t_reencode_staged_ms": t_e * 1e3,
+               "update_GBps": fbytes / t_u / 1e9, "reencode_recon_GBps": fbytes / t_r / 1e9,
+               "reencode_staged_GBps": fbytes / t_e / 1e9,
+               "update_hbm_fraction": moved / t_u / HBM,
+               "recon_over_update": t_r / t_u, "staged_over_update": t_e / t_u,
+               "spread_update": fg["update"]["spread"], "spread_reencode_recon": fg["reencode_recon"]["spread"],
+               "spread_reencode_staged": fg["reencode_staged"]["spread"],
+               "iters": {k: v["iters"] for k, v in fg.items()}}
+        out["results"].append(rec)
+        print(json.dumps(rec), flush=True)
+        del shards, frames, good, old, newsyms, plan, reenc, c
+        torch.cuda.empty_cache()
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print("wrote", args.out)
+
+
+if __name__ == "__main__":
+    main()
