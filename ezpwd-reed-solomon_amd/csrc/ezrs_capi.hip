@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <new>
 #include <string>
 #include <thread>
@@ -51,20 +52,24 @@ struct ezrs_codec {
     mutable std::vector<void *> ws_retired;
 };
 
-// A reconstruction plan: one loss pattern of one codec and length.  It holds copies of what it needs
-// from the codec and is const after ezrs_recon_create.
-struct ezrs_recon {
+// What the plans of the frame-in-place kernels share: copies of what they need from the codec, and
+// the device table (recon_table).  A plan is const after its *_create.
+struct FramePlan {
     int device = 0;
-    unsigned mm = 0, nroots = 0, len = 0, nlost = 0, nsurv = 0;
-    uint32_t *d_tab = nullptr;    // recon_table
+    unsigned mm = 0, nroots = 0, len = 0;
+    uint32_t *d_tab = nullptr;
+    virtual ~FramePlan() = default;   // destroy_plan deletes either plan through this type
 };
 
-// A parity-update plan: one set of changed data positions of one codec and length; const after
-// ezrs_update_create.
-struct ezrs_update {
-    int device = 0;
-    unsigned mm = 0, nroots = 0, len = 0, nchg = 0;
-    uint32_t *d_tab = nullptr;    // recon_table with survivors = changed, lost = the parity positions
+// A reconstruction plan: one loss pattern of one codec and length.
+struct ezrs_recon : FramePlan {
+    unsigned nlost = 0, nsurv = 0;
+};
+
+// A parity-update plan: one set of changed data positions of one codec and length.  Its table has
+// survivors = changed, lost = the parity positions.
+struct ezrs_update : FramePlan {
+    unsigned nchg = 0;
 };
 
 namespace {
@@ -587,14 +592,24 @@ size_t il_ws_bytes(const ezrs_codec *c, unsigned len, size_t ncw) {
     return il_ws_codec(c, chunk) + il_stage_bytes(chunk, (size_t)len + c->dev.nroots, w);
 }
 
-// Argument checks shared by the interleaved calls; ncw = nframes * depth.
-int il_check(const ezrs_codec *c, const void *frames, size_t frame_pitch, size_t sym_stride,
-             size_t depth, unsigned len, size_t nframes, size_t &ncw) {
-    if (!c || !frames || depth == 0 || sym_stride < depth) return -EINVAL;
-    if (len < 1 || len > c->dev.load) return -EINVAL;
-    const size_t ns = (size_t)len + c->dev.nroots;
+// The geometry of nframes >= 1 frames of ns symbol rows (every call that takes frames): the rows
+// of a frame and the frames must not overlap, and nframes * depth must fit.  The pitch of a single
+// frame is not used and is set to 0.
+int frames_check(const void *frames, size_t &frame_pitch, size_t sym_stride, size_t depth, size_t ns,
+                 size_t nframes) {
+    if (!frames || depth == 0 || sym_stride < depth) return -EINVAL;
     if (nframes > 1 && frame_pitch < (ns - 1) * sym_stride + depth) return -EINVAL;
     if (depth > SIZE_MAX / nframes) return -EINVAL;
+    if (nframes == 1) frame_pitch = 0;
+    return 0;
+}
+
+// Argument checks shared by the interleaved calls; ncw = nframes * depth.
+int il_check(const ezrs_codec *c, const void *frames, size_t &frame_pitch, size_t sym_stride,
+             size_t depth, unsigned len, size_t nframes, size_t &ncw) {
+    if (!c || len < 1 || len > c->dev.load) return -EINVAL;
+    if (int r = frames_check(frames, frame_pitch, sym_stride, depth, (size_t)len + c->dev.nroots, nframes))
+        return r;
     ncw = depth * nframes;
     return 0;
 }
@@ -611,7 +626,6 @@ int il_run(const ezrs_codec *c, void *frames, size_t frame_pitch, size_t sym_str
     const unsigned NR = c->dev.nroots;
     const size_t w = sym_bytes(c->dev), P = (size_t)len + NR;
     const size_t chunk = il_chunk_rows(c, len, ncw);
-    if (ncw == depth) frame_pitch = 0;              // one frame: its pitch is not used
     char *stage =static_cast<char *>(ws) + il_ws_codec(c, chunk);
     for (size_t k0 = 0; k0 < ncw; k0 += chunk) {
         const size_t n = ncw - k0 < chunk ? ncw - k0 : chunk;
@@ -685,7 +699,57 @@ int ezrs_decode_interleaved(const ezrs_codec *c, void *frames, size_t frame_pitc
     return il_call(c, frames, frame_pitch, sym_stride, depth, len, nframes, &o, nullptr, stream);
 }
 
-// ---- shared-erasure reconstruction --------------------------------------------------------------
+// ---- plans of the frame-in-place kernels: shared-erasure reconstruction, in-place parity update ----
+namespace {
+
+int upload_table(FramePlan *p, const std::vector<uint32_t> &tab, const char *what) {
+    DeviceGuard g(p->device);
+    const size_t bytes = tab.size() * sizeof(uint32_t);
+    hipError_t e;
+    if ((e = hipMalloc(&p->d_tab, bytes)) != hipSuccess ||
+        (e = hipMemcpy(p->d_tab, tab.data(), bytes, hipMemcpyHostToDevice)) != hipSuccess)
+        return hip_fail(e, what);
+    return 0;
+}
+
+int destroy_plan(FramePlan *p) {
+    if (!p) return 0;
+    DeviceGuard g(p->device);
+    if (p->d_tab) (void)hipFree(p->d_tab);
+    delete p;
+    return 0;
+}
+
+// What ezrs_recon_create and ezrs_update_create share once their arguments are checked.  p: the new
+// plan (null: out of memory), destroyed here on failure; kind: its name in the error texts; ncols,
+// nlost: the table's survivors and lost positions; table(tab): builds it, false for bad arguments.
+int init_plan(FramePlan *p, const ezrs_codec *c, unsigned len, const char *kind, unsigned ncols,
+              unsigned nlost, const std::function<bool(std::vector<uint32_t> &)> &table) {
+    const CodecSpec &spec = c->math.spec;
+    int r = p ? 0 : -ENOMEM;
+    if (recon_table_words(spec.mm, spec.nroots, ncols, nlost) * sizeof(uint32_t) > kReconMaxTable) {
+        g_last_error = std::string(kind) + " plan: device table above 64 MiB";
+        r = -ENOTSUP;
+    }
+    std::vector<uint32_t> tab;
+    try {
+        if (!r && !table(tab)) r = -EINVAL;
+    } catch (const std::bad_alloc &) {
+        r = -ENOMEM;
+    }
+    if (!r) {
+        p->device = c->device;
+        p->mm = spec.mm;
+        p->nroots = spec.nroots;
+        p->len = len;
+        r = upload_table(p, tab, ("hipMalloc(" + std::string(kind) + " table)").c_str());
+    }
+    if (r) destroy_plan(p);
+    return r;
+}
+
+} // namespace
+
 int ezrs_recon_create(ezrs_recon **out, const ezrs_codec *c, unsigned len, const uint32_t *lost,
                       unsigned nlost) {
     if (!out) return -EINVAL;
@@ -698,70 +762,37 @@ int ezrs_recon_create(ezrs_recon **out, const ezrs_codec *c, unsigned len, const
         return -EINVAL;
     }
     const unsigned NR = m.spec.nroots, nsurv = len + NR - nlost;
-    const size_t words = recon_table_words(m.spec.mm, NR, nsurv, nlost);
-    if (words * sizeof(uint32_t) > kReconMaxTable) {
-        g_last_error = "reconstruction plan: device table above 64 MiB";
-        return -ENOTSUP;
-    }
-    ezrs_recon *p = nullptr;
-    std::vector<uint32_t> tab;
-    try {
-        p = new ezrs_recon;
+    ezrs_recon *p = new (std::nothrow) ezrs_recon;
+    const int r = init_plan(p, c, len, "reconstruction", nsurv, nlost, [&](std::vector<uint32_t> &tab) {
         std::vector<uint16_t> cols;
         std::vector<uint32_t> surv;
-        if (!recon_build(m, len, lost, nlost, cols, surv)) {
-            delete p;
-            return -EINVAL;
-        }
+        if (!recon_build(m, len, lost, nlost, cols, surv)) return false;
         recon_table(m.spec.mm, NR, cols, surv, lost, nlost, tab);
-    } catch (const std::bad_alloc &) {
-        delete p;
-        return -ENOMEM;
-    }
-    p->device = c->device;
-    p->mm = m.spec.mm;
-    p->nroots = NR;
-    p->len = len;
+        return true;
+    });
+    if (r) return r;
     p->nlost = nlost;
     p->nsurv = nsurv;
-    DeviceGuard g(c->device);
-    hipError_t e;
-    if ((e = hipMalloc(&p->d_tab, tab.size() * sizeof(uint32_t))) != hipSuccess ||
-        (e = hipMemcpy(p->d_tab, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice)) !=
-            hipSuccess) {
-        ezrs_recon_destroy(p);
-        return hip_fail(e, "hipMalloc(reconstruction table)");
-    }
     *out = p;
     return 0;
 }
 
-int ezrs_recon_destroy(ezrs_recon *p) {
-    if (!p) return 0;
-    DeviceGuard g(p->device);
-    if (p->d_tab) (void)hipFree(p->d_tab);
-    delete p;
-    return 0;
-}
+int ezrs_recon_destroy(ezrs_recon *p) { return destroy_plan(p); }
 
 int ezrs_reconstruct_interleaved(const ezrs_recon *p, void *frames, size_t frame_pitch, size_t sym_stride,
                                  size_t depth, size_t nframes, int32_t *result, void *stream) {
     if (!p) return -EINVAL;
     if (nframes == 0) return 0;
-    if (!frames || depth == 0 || sym_stride < depth) return -EINVAL;
-    const size_t ns = (size_t)p->len + p->nroots;
-    if (nframes > 1 && frame_pitch < (ns - 1) * sym_stride + depth) return -EINVAL;
-    if (depth > SIZE_MAX / nframes) return -EINVAL;
-    if (nframes == 1) frame_pitch = 0;              // one frame: its pitch is not used
+    if (int r = frames_check(frames, frame_pitch, sym_stride, depth, (size_t)p->len + p->nroots, nframes)) return r;
     DeviceGuard g(p->device);
-    ReconArgs a{frames, frame_pitch, sym_stride, depth, 0, 0, 0, 0, result, p->nsurv, p->nlost, p->mm,
+    ReconArgs a{{frames, frame_pitch, sym_stride, depth, 0, 0, 0, 0}, result, p->nsurv, p->nlost, p->mm,
                 recon_row_pad(p->nroots), result ? p->nroots : p->nlost};
-    hipError_t e = launch_recon(a, nframes, p->d_tab, static_cast<hipStream_t>(stream));
+    const DevTable t = table_view<const uint32_t>(p->d_tab, p->mm, p->nroots, p->nsurv, p->nlost);
+    hipError_t e = launch_recon(a, nframes, t, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return hip_fail(e, "reconstruction launch");
     return 0;
 }
 
-// ---- in-place parity update -----------------------------------------------------------------------
 int ezrs_update_create(ezrs_update **out, const ezrs_codec *c, unsigned len, const uint32_t *changed,
                        unsigned nchanged) {
     if (!out) return -EINVAL;
@@ -774,68 +805,35 @@ int ezrs_update_create(ezrs_update **out, const ezrs_codec *c, unsigned len, con
         return -EINVAL;
     }
     const unsigned NR = m.spec.nroots;
-    const size_t words = recon_table_words(m.spec.mm, NR, nchanged, NR);
-    if (words * sizeof(uint32_t) > kReconMaxTable) {
-        g_last_error = "update plan: device table above 64 MiB";
-        return -ENOTSUP;
-    }
-    ezrs_update *p = nullptr;
-    std::vector<uint32_t> tab;
-    try {
-        p = new ezrs_update;
+    ezrs_update *p = new (std::nothrow) ezrs_update;
+    const int r = init_plan(p, c, len, "update", nchanged, NR, [&](std::vector<uint32_t> &tab) {
         std::vector<uint16_t> cols;
-        if (!update_build(m, len, changed, nchanged, cols)) {
-            delete p;
-            return -EINVAL;
-        }
+        if (!update_build(m, len, changed, nchanged, cols)) return false;
         std::vector<uint32_t> par(NR);
         for (unsigned i = 0; i < NR; ++i) par[i] = len + i;
         recon_table(m.spec.mm, NR, cols, std::vector<uint32_t>(changed, changed + nchanged), par.data(), NR, tab);
-    } catch (const std::bad_alloc &) {
-        delete p;
-        return -ENOMEM;
-    }
-    p->device = c->device;
-    p->mm = m.spec.mm;
-    p->nroots = NR;
-    p->len = len;
+        return true;
+    });
+    if (r) return r;
     p->nchg = nchanged;
-    DeviceGuard g(c->device);
-    hipError_t e;
-    if ((e = hipMalloc(&p->d_tab, tab.size() * sizeof(uint32_t))) != hipSuccess ||
-        (e = hipMemcpy(p->d_tab, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice)) !=
-            hipSuccess) {
-        ezrs_update_destroy(p);
-        return hip_fail(e, "hipMalloc(update table)");
-    }
     *out = p;
     return 0;
 }
 
-int ezrs_update_destroy(ezrs_update *p) {
-    if (!p) return 0;
-    DeviceGuard g(p->device);
-    if (p->d_tab) (void)hipFree(p->d_tab);
-    delete p;
-    return 0;
-}
+int ezrs_update_destroy(ezrs_update *p) { return destroy_plan(p); }
 
 int ezrs_update_interleaved(const ezrs_update *p, void *frames, size_t frame_pitch, size_t sym_stride,
                             size_t depth, size_t nframes, const void *newsyms, size_t new_frame_pitch,
                             size_t new_sym_stride, void *stream) {
     if (!p) return -EINVAL;
     if (nframes == 0) return 0;
-    if (!frames || !newsyms || depth == 0 || sym_stride < depth || new_sym_stride < depth) return -EINVAL;
-    const size_t ns = (size_t)p->len + p->nroots;
-    if (nframes > 1 && (frame_pitch < (ns - 1) * sym_stride + depth ||
-                        new_frame_pitch < (size_t)(p->nchg - 1) * new_sym_stride + depth))
-        return -EINVAL;
-    if (depth > SIZE_MAX / nframes) return -EINVAL;
-    if (nframes == 1) frame_pitch = new_frame_pitch = 0;   // one frame: the pitches are not used
+    if (int r = frames_check(frames, frame_pitch, sym_stride, depth, (size_t)p->len + p->nroots, nframes)) return r;
+    if (int r = frames_check(newsyms, new_frame_pitch, new_sym_stride, depth, p->nchg, nframes)) return r;
     DeviceGuard g(p->device);
-    UpdateArgs a{frames, frame_pitch, sym_stride, depth, 0, 0, 0, 0, newsyms, new_frame_pitch, new_sym_stride,
+    UpdateArgs a{{frames, frame_pitch, sym_stride, depth, 0, 0, 0, 0}, newsyms, new_frame_pitch, new_sym_stride,
                  p->nchg, p->len, p->nroots, p->mm, recon_row_pad(p->nroots)};
-    hipError_t e = launch_update(a, nframes, p->d_tab, static_cast<hipStream_t>(stream));
+    const DevTable t = table_view<const uint32_t>(p->d_tab, p->mm, p->nroots, p->nchg, p->nroots);
+    hipError_t e = launch_update(a, nframes, t, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return hip_fail(e, "update launch");
     return 0;
 }

@@ -200,28 +200,29 @@ hipError_t launch_il_scatter(const DevCodec &d, const IlArgs &a, hipStream_t s);
 // rebuild lost[0..nlost-1], the others are check rows), and the surviving positions, ascending;
 // false for a bad length or loss list (recon_check).  recon_table: the device table of a plan,
 // coefficients | survivors | lost | the per-row constant the kernel takes out of its accumulators
-// at the end; coefficients for m > 8: [survivor][bit][recon_row_pad(nroots)] columns replicated
-// across a dword, for m <= 8: [survivor][group of 3 bits][recon_row_pad(nroots)][2] dwords, the
-// images of the group's 8 values as bytes.
+// at the end (table_view: the four parts from the table's base); coefficients for m > 8:
+// [survivor][bit][recon_row_pad(nroots)] columns replicated across a dword, for m <= 8:
+// [survivor][group of 3 bits][recon_row_pad(nroots)][2] dwords, the images of the group's 8 values
+// as bytes.
 bool recon_check(const CodecMath &m, unsigned len, const uint32_t *lost, unsigned nlost);
 bool recon_build(const CodecMath &m, unsigned len, const uint32_t *lost, unsigned nlost,
                  std::vector<uint16_t> &cols, std::vector<uint32_t> &surv);
 unsigned recon_row_pad(unsigned nroots);
+size_t recon_coef_words(unsigned mm, unsigned nroots, unsigned nsurv);
 size_t recon_table_words(unsigned mm, unsigned nroots, unsigned nsurv, unsigned nlost);
 void recon_table(unsigned mm, unsigned nroots, const std::vector<uint16_t> &cols,
                  const std::vector<uint32_t> &surv, const uint32_t *lost, unsigned nlost,
                  std::vector<uint32_t> &tab);
-struct ReconArgs {
-    void *frames;
-    size_t frame_pitch, sym_stride, depth;
-    size_t j0, runs;              // set per launch: first codeword of a frame, lanes per frame
-    size_t f0, nf;                // set per launch: frames
-    int32_t *result;              // nullable
-    unsigned nsurv, nlost, mm;
-    unsigned nrp;                 // recon_row_pad(nroots)
-    unsigned nrows;               // rows to apply: nroots, or nlost when result is null
+template <class W>
+struct TableView {
+    W *K, *pos, *lost, *fix;      // coefficients | survivors [nsurv] | lost [nlost] | fix [row pad]
 };
-hipError_t launch_recon(const ReconArgs &a, size_t nframes, const uint32_t *tab, hipStream_t s);
+template <class W>
+inline TableView<W> table_view(W *tab, unsigned mm, unsigned nroots, unsigned nsurv, unsigned nlost) {
+    W *const pos = tab + recon_coef_words(mm, nroots, nsurv);
+    return {tab, pos, pos + nsurv, pos + nsurv + nlost};
+}
+using DevTable = TableView<const uint32_t>;
 
 // In-place parity update of interleaved frames (ezrs_recon.hip; ezrs_update_create /
 // ezrs_update_interleaved): the code is linear, so parity_new = parity_old ^ G[:, changed] *
@@ -233,16 +234,32 @@ hipError_t launch_recon(const ReconArgs &a, size_t nframes, const uint32_t *tab,
 bool update_check(const CodecMath &m, unsigned len, const uint32_t *changed, unsigned nchanged);
 bool update_build(const CodecMath &m, unsigned len, const uint32_t *changed, unsigned nchanged,
                   std::vector<uint16_t> &cols);
-struct UpdateArgs {
+
+// What the two frame-in-place kernels work on: the frames as in IlArgs (strides in elements) and,
+// set per launch by the launcher, the part of them a launch covers.  First member of both argument
+// structs.
+struct FrameSpan {
     void *frames;
     size_t frame_pitch, sym_stride, depth;
-    size_t j0, runs;              // set per launch: first codeword of a frame, lanes per frame
-    size_t f0, nf;                // set per launch: frames
+    size_t j0, runs;              // first codeword of a frame, lanes per frame
+    size_t f0, nf;                // frames
+};
+struct ReconArgs {
+    FrameSpan span;
+    int32_t *result;              // nullable
+    unsigned nsurv, nlost, mm;
+    unsigned nrp;                 // recon_row_pad(nroots)
+    unsigned nrows;               // rows to apply: nroots, or nlost when result is null
+};
+struct UpdateArgs {
+    FrameSpan span;
     const void *newsyms;          // [frame][changed position][codeword]
     size_t new_frame_pitch, new_sym_stride;
     unsigned nchg, len, nroots, mm;
     unsigned nrp;                 // recon_row_pad(nroots)
 };
-hipError_t launch_update(const UpdateArgs &a, size_t nframes, const uint32_t *tab, hipStream_t s);
+// t: the plan's device table (table_view of its base).
+hipError_t launch_recon(const ReconArgs &a, size_t nframes, const DevTable &t, hipStream_t s);
+hipError_t launch_update(const UpdateArgs &a, size_t nframes, const DevTable &t, hipStream_t s);
 
 } // namespace ezrs

@@ -151,7 +151,7 @@ unsigned recon_row_pad(unsigned nroots) {
 // Dwords of the coefficient part of the table.  m <= 8: per survivor, group of three symbol bits and
 // row, the 8 byte-wide images of the group's values (two dwords; apply8).  m > 8: per survivor, bit
 // and row, the bit's column replicated across the dword (apply).
-static size_t recon_coef_words(unsigned mm, unsigned nroots, unsigned nsurv) {
+size_t recon_coef_words(unsigned mm, unsigned nroots, unsigned nsurv) {
     const size_t per = mm <= 8 ? (size_t)((mm + 2) / 3) * 2 : mm;
     return (size_t)nsurv * per * recon_row_pad(nroots);
 }
@@ -165,9 +165,9 @@ void recon_table(unsigned mm, unsigned nroots, const std::vector<uint16_t> &cols
                  std::vector<uint32_t> &tab) {
     const unsigned nsurv = (unsigned)surv.size(), nrp = recon_row_pad(nroots);
     tab.assign(recon_table_words(mm, nroots, nsurv, nlost), 0);
-    uint32_t *tail = tab.data() + recon_coef_words(mm, nroots, nsurv);
-    std::copy(surv.begin(), surv.end(), tail);
-    std::copy(lost, lost + nlost, tail + nsurv);
+    const TableView<uint32_t> t = table_view(tab.data(), mm, nroots, nsurv, nlost);
+    std::copy(surv.begin(), surv.end(), t.pos);
+    std::copy(lost, lost + nlost, t.lost);
     if (mm <= 8) {
         const unsigned G = (mm + 2) / 3;
         for (unsigned r = 0; r < nroots; ++r)
@@ -187,9 +187,8 @@ void recon_table(unsigned mm, unsigned nroots, const std::vector<uint16_t> &cols
         for (unsigned c = 0; c < nsurv; ++c)
             for (unsigned b = 0; b < mm; ++b)
                 tab[((size_t)c * mm + b) * nrp + r] = cols[((size_t)r * nsurv + c) * mm + b] * 0x00010001u;
-    uint32_t *fix = tail + nsurv + nlost;           // see apply()
-    for (size_t i = 0; i < (size_t)nsurv * mm; ++i)
-        for (unsigned r = 0; r < nrp; ++r) fix[r] ^= tab[i * nrp + r] & 0x7fff7fffu;
+    for (size_t i = 0; i < (size_t)nsurv * mm; ++i)   // see apply()
+        for (unsigned r = 0; r < nrp; ++r) t.fix[r] ^= tab[i * nrp + r] & 0x7fff7fffu;
 }
 
 bool update_check(const CodecMath &m, unsigned len, const uint32_t *changed, unsigned nchanged) {
@@ -244,6 +243,25 @@ struct Run {
         else *p = (T)x[0];
     }
 };
+
+// The lane map of the frame-in-place kernels: thread t = lane_index() of a launch takes run
+// t % runs (epl codewords from codeword j) of frame f = f0 + t / runs.  The threads at and past
+// runs * nf have no run: the kernels return on them before they ask (with that test in here
+// k_recon<uint8_t, 4, 4> compiles to other registers and another occupancy).
+__device__ __forceinline__ size_t lane_index() { return (size_t)blockIdx.x * 256 + threadIdx.x; }
+__device__ __forceinline__ void lane(const FrameSpan &a, size_t t, unsigned epl, size_t &f, size_t &j) {
+    size_t q;
+    if (((t | a.runs) >> 32) == 0) {                // 32-bit division (see shard_row)
+        const uint32_t t32 = (uint32_t)t, r32 = (uint32_t)a.runs, f32 = t32 / r32;
+        f = f32;
+        q = t32 - f32 * r32;
+    } else {
+        f = t / a.runs;
+        q = t - f * a.runs;
+    }
+    f += a.f0;
+    j = a.j0 + q * epl;
+}
 
 // One survivor's dwords x into the accumulators of a row block; kp: its columns, bit b at
 // kp + b * nrp.  MB: the symbol bits when known at compile time (the bit loop is then unrolled and
@@ -379,7 +397,7 @@ __device__ __forceinline__ void sweep(const ReconArgs &a, const T *base, const u
     for (; c + kUnroll <= a.nsurv; c += kUnroll) {
         uint32_t x[kUnroll][ND];
 #pragma unroll
-        for (unsigned u = 0; u < kUnroll; ++u) R::load(base + (size_t)surv[c + u] * a.sym_stride, x[u]);
+        for (unsigned u = 0; u < kUnroll; ++u) R::load(base + (size_t)surv[c + u] * a.span.sym_stride, x[u]);
         if constexpr (BYTES && MB == 8) {
 #pragma unroll
             for (unsigned u = 0; u < kUnroll; u += 2)
@@ -391,7 +409,7 @@ __device__ __forceinline__ void sweep(const ReconArgs &a, const T *base, const u
     }
     for (; c < a.nsurv; ++c) {
         uint32_t x[ND];
-        R::load(base + (size_t)surv[c] * a.sym_stride, x);
+        R::load(base + (size_t)surv[c] * a.span.sym_stride, x);
         one(x, c);
     }
 }
@@ -405,19 +423,11 @@ __global__ void __launch_bounds__(256) k_recon(ReconArgs a, const uint32_t *__re
     using R = Run<T, V>;
     constexpr int ND = R::ND;
     constexpr unsigned W = 8 * sizeof(T);
-    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= a.runs * a.nf) return;
-    size_t f, q;
-    if (((t | a.runs) >> 32) == 0) {                // 32-bit division (see shard_row)
-        const uint32_t t32 = (uint32_t)t, r32 = (uint32_t)a.runs, f32 = t32 / r32;
-        f = f32;
-        q = t32 - f32 * r32;
-    } else {
-        f = t / a.runs;
-        q = t - f * a.runs;
-    }
-    const size_t j = a.j0 + q * R::EPL;
-    T *const base = static_cast<T *>(a.frames) + (a.f0 + f) * a.frame_pitch + j;
+    const size_t t = lane_index();
+    if (t >= a.span.runs * a.span.nf) return;
+    size_t f, j;
+    lane(a.span, t, R::EPL, f, j);
+    T *const base = static_cast<T *>(a.span.frames) + f * a.span.frame_pitch + j;
     uint32_t bad[ND];
 #pragma unroll
     for (int d = 0; d < ND; ++d) bad[d] = 0;
@@ -436,7 +446,7 @@ __global__ void __launch_bounds__(256) k_recon(ReconArgs a, const uint32_t *__re
 #pragma unroll
             for (int d = 0; d < ND; ++d) acc[r][d] ^= fx;
             if (row < a.nlost) {
-                R::store(base + (size_t)lost[row] * a.sym_stride, acc[r]);
+                R::store(base + (size_t)lost[row] * a.span.sym_stride, acc[r]);
             } else {                                // check rows; the padding rows are zero
 #pragma unroll
                 for (int d = 0; d < ND; ++d) bad[d] |= acc[r][d];
@@ -444,7 +454,7 @@ __global__ void __launch_bounds__(256) k_recon(ReconArgs a, const uint32_t *__re
         }
     }
     if (a.result) {
-        int32_t *res = a.result + (a.f0 + f) * a.depth + j;
+        int32_t *res = a.result + f * a.span.depth + j;
         constexpr unsigned EPD = V ? 4 / sizeof(T) : 1;
 #pragma unroll
         for (int d = 0; d < ND; ++d)
@@ -454,70 +464,6 @@ __global__ void __launch_bounds__(256) k_recon(ReconArgs a, const uint32_t *__re
                 res[d * EPD + e] = v ? -1 : (int32_t)a.nlost;
             }
     }
-}
-
-template <typename T, int V>
-static void launch_rb(unsigned rb, dim3 grid, hipStream_t s, const ReconArgs &a, const uint32_t *K,
-                      const uint32_t *surv, const uint32_t *lost, const uint32_t *fix) {
-    const dim3 block(256);
-    switch (rb) {
-    case 4: hipLaunchKernelGGL((k_recon<T, 4, V>), grid, block, 0, s, a, K, surv, lost, fix); break;
-    case 8: hipLaunchKernelGGL((k_recon<T, 8, V>), grid, block, 0, s, a, K, surv, lost, fix); break;
-    case 16: hipLaunchKernelGGL((k_recon<T, 16, V>), grid, block, 0, s, a, K, surv, lost, fix); break;
-    default:                                        // 32 rows: the bit-column form only (launch())
-        if constexpr (sizeof(T) == 2) hipLaunchKernelGGL((k_recon<T, 32, V>), grid, block, 0, s, a, K, surv, lost, fix);
-        break;
-    }
-}
-
-// Codewords [j0, j0 + n) of every frame, `epl` per lane.
-template <typename T, int V>
-static hipError_t launch_span(ReconArgs a, unsigned rb, size_t j0, size_t n, size_t nframes,
-                              const uint32_t *tab, hipStream_t s) {
-    constexpr size_t EPL = Run<T, V>::EPL;
-    if (!n) return hipSuccess;
-    a.j0 = j0;
-    a.runs = n / EPL;
-    const size_t per = a.mm <= 8 ? (size_t)((a.mm + 2) / 3) * 2 : a.mm;   // recon_coef_words
-    const uint32_t *K = tab, *surv = tab + (size_t)a.nsurv * per * a.nrp, *lost = surv + a.nsurv,
-                   *fix = lost + a.nlost;
-    const size_t maxt = (size_t)1 << 38;            // threads per launch (2^30 workgroups)
-    if (a.runs > maxt) return hipErrorInvalidValue;
-    const size_t fstep = maxt / a.runs;
-    for (size_t f0 = 0; f0 < nframes; f0 += fstep) {
-        a.f0 = f0;
-        a.nf = nframes - f0 < fstep ? nframes - f0 : fstep;
-        const dim3 grid((unsigned)((a.runs * a.nf + 255) / 256));
-        launch_rb<T, V>(rb, grid, s, a, K, surv, lost, fix);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
-template <typename T>
-static hipError_t launch(ReconArgs a, size_t nframes, const uint32_t *tab, hipStream_t s) {
-    // rows per block: the byte form stops at 16 (at 32 its 192 table dwords per survivor no longer
-    // fit the scalar registers and the kernel ran 1.5 x slower than two passes of 16)
-    const unsigned cap = sizeof(T) == 1 ? 16 : 32;
-    unsigned rb = 4;
-    while (rb < cap && rb < a.nrows) rb *= 2;
-    // widest access every symbol row of every frame is aligned for
-    const size_t w = sizeof(T);
-    size_t al = (size_t)(uintptr_t)a.frames | a.sym_stride * w;
-    if (nframes > 1) al |= a.frame_pitch * w;
-    const size_t e16 = 16 / w, e4 = 4 / w;
-    size_t done = 0;
-    hipError_t e = hipSuccess;
-    if ((al & 15) == 0 && a.depth >= e16) {
-        done = a.depth / e16 * e16;
-        e = launch_span<T, 4>(a, rb, 0, done, nframes, tab, s);
-    } else if ((al & 3) == 0 && a.depth >= e4) {
-        done = a.depth / e4 * e4;
-        e = launch_span<T, 1>(a, rb, 0, done, nframes, tab, s);
-    }
-    if (e == hipSuccess) e = launch_span<T, 0>(a, rb, done, a.depth - done, nframes, tab, s);   // ragged end
-    return e;
 }
 
 // ---- in-place parity update (ezrs_update_interleaved) ---------------------------------------------
@@ -536,7 +482,7 @@ __device__ __forceinline__ void udelta(const UpdateArgs &a, const T *base, const
     using R = Run<T, V>;
 #pragma unroll
     for (int u = 0; u < N; ++u) {
-        R::load(base + (size_t)chg[c0 + u] * a.sym_stride, d[u]);
+        R::load(base + (size_t)chg[c0 + u] * a.span.sym_stride, d[u]);
         R::load(nbase + (size_t)(c0 + u) * a.new_sym_stride, nw[u]);
     }
 #pragma unroll
@@ -616,7 +562,7 @@ __device__ __forceinline__ void ubody(const UpdateArgs &a, const uint32_t *__res
                                       T *base, const T *nbase) {
     using R = Run<T, V>;
     constexpr int ND = R::ND;
-    T *const par = base + (size_t)a.len * a.sym_stride;
+    T *const par = base + (size_t)a.len * a.span.sym_stride;
     uint32_t d[NC ? NC : 1][ND], nw[NC ? NC : 1][ND];
     if constexpr (NC != 0) udelta<T, V, NC>(a, base, nbase, chg, 0, d, nw);
     auto block = [&](unsigned r0) {
@@ -629,7 +575,7 @@ __device__ __forceinline__ void ubody(const UpdateArgs &a, const uint32_t *__res
 #pragma unroll
             for (int r = 0; r < RB; ++r) {
                 const unsigned row = r0 + r < a.nroots ? r0 + r : a.nroots - 1;
-                R::load(par + (size_t)row * a.sym_stride, acc[r]);
+                R::load(par + (size_t)row * a.span.sym_stride, acc[r]);
             }
         } else {
 #pragma unroll
@@ -643,7 +589,7 @@ __device__ __forceinline__ void ubody(const UpdateArgs &a, const uint32_t *__res
 #pragma unroll
         for (int r = 0; r < RB; ++r)
             if (r0 + r < a.nroots) {
-                T *const p = par + (size_t)(r0 + r) * a.sym_stride;
+                T *const p = par + (size_t)(r0 + r) * a.span.sym_stride;
                 const uint32_t fx = fix[r0 + r];
                 if constexpr (uearly(RB * ND)) {
 #pragma unroll
@@ -660,13 +606,13 @@ __device__ __forceinline__ void ubody(const UpdateArgs &a, const uint32_t *__res
     if constexpr (NC != 0) {
         block(0);
 #pragma unroll
-        for (int u = 0; u < NC; ++u) R::store(base + (size_t)chg[u] * a.sym_stride, nw[u]);
+        for (int u = 0; u < NC; ++u) R::store(base + (size_t)chg[u] * a.span.sym_stride, nw[u]);
     } else {
         for (unsigned r0 = 0; r0 < a.nroots; r0 += RB) block(r0);
         for (unsigned c = 0; c < a.nchg; ++c) {
             uint32_t x[ND];
             R::load(nbase + (size_t)c * a.new_sym_stride, x);
-            R::store(base + (size_t)chg[c] * a.sym_stride, x);
+            R::store(base + (size_t)chg[c] * a.span.sym_stride, x);
         }
     }
 }
@@ -677,20 +623,12 @@ __global__ void __launch_bounds__(256) k_update(UpdateArgs a, const uint32_t *__
                                                 const uint32_t *__restrict__ chg,
                                                 const uint32_t *__restrict__ fix) {
     using R = Run<T, V>;
-    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= a.runs * a.nf) return;
-    size_t f, q;
-    if (((t | a.runs) >> 32) == 0) {                // 32-bit division (see shard_row)
-        const uint32_t t32 = (uint32_t)t, r32 = (uint32_t)a.runs, f32 = t32 / r32;
-        f = f32;
-        q = t32 - f32 * r32;
-    } else {
-        f = t / a.runs;
-        q = t - f * a.runs;
-    }
-    const size_t j = a.j0 + q * R::EPL;
-    T *const base = static_cast<T *>(a.frames) + (a.f0 + f) * a.frame_pitch + j;
-    const T *const nbase = static_cast<const T *>(a.newsyms) + (a.f0 + f) * a.new_frame_pitch + j;
+    const size_t t = lane_index();
+    if (t >= a.span.runs * a.span.nf) return;
+    size_t f, j;
+    lane(a.span, t, R::EPL, f, j);
+    T *const base = static_cast<T *>(a.span.frames) + f * a.span.frame_pitch + j;
+    const T *const nbase = static_cast<const T *>(a.newsyms) + f * a.new_frame_pitch + j;
     static_assert(kUnroll == 4, "one case per count of changed positions kept in registers");
     constexpr unsigned KEEP = ukeep(RB * R::ND);
     const unsigned nc = a.nroots <= RB && a.nchg <= KEEP ? a.nchg : 0;
@@ -707,78 +645,104 @@ __global__ void __launch_bounds__(256) k_update(UpdateArgs a, const uint32_t *__
     }
 }
 
-template <typename T, int V>
-static void ulaunch_rb(unsigned rb, dim3 grid, hipStream_t s, const UpdateArgs &a, const uint32_t *K,
-                       const uint32_t *chg, const uint32_t *fix) {
-    const dim3 block(256);
+// Rows per block of a plan of nrows rows: 4, 8, 16 and, for 16-bit symbols only, 32.  The byte form
+// stops at 16 (at 32 its 192 table dwords per survivor no longer fit the scalar registers and the
+// kernel ran 1.5 x slower than two passes of 16).
+template <typename T>
+static unsigned rows_per_block(unsigned nrows) {
+    const unsigned cap = sizeof(T) == 1 ? 16 : 32;
+    unsigned rb = 4;
+    while (rb < cap && rb < nrows) rb *= 2;
+    return rb;
+}
+
+// f(RB) with the row block rb as a compile-time constant.
+template <typename T, class F>
+static void with_rb(unsigned rb, F &&f) {
     switch (rb) {
-    case 4: hipLaunchKernelGGL((k_update<T, 4, V>), grid, block, 0, s, a, K, chg, fix); break;
-    case 8: hipLaunchKernelGGL((k_update<T, 8, V>), grid, block, 0, s, a, K, chg, fix); break;
-    case 16: hipLaunchKernelGGL((k_update<T, 16, V>), grid, block, 0, s, a, K, chg, fix); break;
-    default:                                        // 32 rows: the bit-column form only (ulaunch())
-        if constexpr (sizeof(T) == 2) hipLaunchKernelGGL((k_update<T, 32, V>), grid, block, 0, s, a, K, chg, fix);
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 8: f(std::integral_constant<int, 8>{}); break;
+    case 16: f(std::integral_constant<int, 16>{}); break;
+    default:                                        // 32 rows: the bit-column form only (rows_per_block)
+        if constexpr (sizeof(T) == 2) f(std::integral_constant<int, 32>{});
         break;
     }
 }
 
-// Codewords [j0, j0 + n) of every frame, as launch_span.
-template <typename T, int V>
-static hipError_t ulaunch_span(UpdateArgs a, unsigned rb, size_t j0, size_t n, size_t nframes,
-                               const uint32_t *tab, hipStream_t s) {
-    constexpr size_t EPL = Run<T, V>::EPL;
-    if (!n) return hipSuccess;
-    a.j0 = j0;
-    a.runs = n / EPL;
-    const size_t per = a.mm <= 8 ? (size_t)((a.mm + 2) / 3) * 2 : a.mm;   // recon_coef_words
-    const uint32_t *K = tab, *chg = tab + (size_t)a.nchg * per * a.nrp, *fix = chg + a.nchg + a.nroots;
-    const size_t maxt = (size_t)1 << 38;            // threads per launch (2^30 workgroups)
-    if (a.runs > maxt) return hipErrorInvalidValue;
-    const size_t fstep = maxt / a.runs;
-    for (size_t f0 = 0; f0 < nframes; f0 += fstep) {
-        a.f0 = f0;
-        a.nf = nframes - f0 < fstep ? nframes - f0 : fstep;
-        const dim3 grid((unsigned)((a.runs * a.nf + 255) / 256));
-        ulaunch_rb<T, V>(rb, grid, s, a, K, chg, fix);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
-template <typename T>
-static hipError_t ulaunch(UpdateArgs a, size_t nframes, const uint32_t *tab, hipStream_t s) {
-    const unsigned cap = sizeof(T) == 1 ? 16 : 32;  // rows per block, as launch()
-    unsigned rb = 4;
-    while (rb < cap && rb < a.nroots) rb *= 2;
-    // widest access every symbol row of every frame is aligned for, in `frames` and in `newsyms`
+// Every codeword of every frame through a frame-in-place kernel.  a: the kernel's arguments, its
+// FrameSpan `span` filled in per launch here; al: what else than the frames has to be aligned for a
+// vector access, OR-ed (addresses and byte strides); kernel(RB, V, grid, a): launches the kernel's
+// <T, RB, V> form.
+template <typename T, class A, class F>
+static hipError_t launch_frames(A a, size_t nframes, unsigned rb, size_t al, F &&kernel) {
+    FrameSpan &sp = a.span;
+    // codewords [j0, j0 + n) of every frame, Run<T, V>::EPL per lane
+    auto span = [&](auto V, size_t j0, size_t n) -> hipError_t {
+        if (!n) return hipSuccess;
+        sp.j0 = j0;
+        sp.runs = n / Run<T, decltype(V)::value>::EPL;
+        const size_t maxt = (size_t)1 << 38;        // threads per launch (2^30 workgroups)
+        if (sp.runs > maxt) return hipErrorInvalidValue;
+        const size_t fstep = maxt / sp.runs;
+        for (size_t f0 = 0; f0 < nframes; f0 += fstep) {
+            sp.f0 = f0;
+            sp.nf = nframes - f0 < fstep ? nframes - f0 : fstep;
+            const dim3 grid((unsigned)((sp.runs * sp.nf + 255) / 256));
+            with_rb<T>(rb, [&](auto RB) { kernel(RB, V, grid, a); });
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    };
+    // widest access every symbol row of every frame is aligned for
     const size_t w = sizeof(T);
-    size_t al = (size_t)(uintptr_t)a.frames | a.sym_stride * w | (size_t)(uintptr_t)a.newsyms |
-                a.new_sym_stride * w;
-    if (nframes > 1) al |= a.frame_pitch * w | a.new_frame_pitch * w;
+    al |= (size_t)(uintptr_t)sp.frames | sp.sym_stride * w;
+    if (nframes > 1) al |= sp.frame_pitch * w;
     const size_t e16 = 16 / w, e4 = 4 / w;
     size_t done = 0;
     hipError_t e = hipSuccess;
-    if ((al & 15) == 0 && a.depth >= e16) {
-        done = a.depth / e16 * e16;
-        e = ulaunch_span<T, 4>(a, rb, 0, done, nframes, tab, s);
-    } else if ((al & 3) == 0 && a.depth >= e4) {
-        done = a.depth / e4 * e4;
-        e = ulaunch_span<T, 1>(a, rb, 0, done, nframes, tab, s);
+    if ((al & 15) == 0 && sp.depth >= e16) {
+        done = sp.depth / e16 * e16;
+        e = span(std::integral_constant<int, 4>{}, 0, done);
+    } else if ((al & 3) == 0 && sp.depth >= e4) {
+        done = sp.depth / e4 * e4;
+        e = span(std::integral_constant<int, 1>{}, 0, done);
     }
-    if (e == hipSuccess) e = ulaunch_span<T, 0>(a, rb, done, a.depth - done, nframes, tab, s);   // ragged end
+    if (e == hipSuccess) e = span(std::integral_constant<int, 0>{}, done, sp.depth - done);   // ragged end
     return e;
+}
+
+template <typename T>
+static hipError_t launch_recon(const ReconArgs &a, size_t nframes, const DevTable &t, hipStream_t s) {
+    return launch_frames<T>(a, nframes, rows_per_block<T>(a.nrows), 0,
+                            [&](auto RB, auto V, dim3 grid, const ReconArgs &b) {
+        hipLaunchKernelGGL((k_recon<T, decltype(RB)::value, decltype(V)::value>), grid, dim3(256), 0, s, b,
+                           t.K, t.pos, t.lost, t.fix);
+    });
+}
+
+template <typename T>
+static hipError_t launch_update(const UpdateArgs &a, size_t nframes, const DevTable &t, hipStream_t s) {
+    // `newsyms` is accessed like the frames
+    size_t al = (size_t)(uintptr_t)a.newsyms | a.new_sym_stride * sizeof(T);
+    if (nframes > 1) al |= a.new_frame_pitch * sizeof(T);
+    return launch_frames<T>(a, nframes, rows_per_block<T>(a.nroots), al,
+                            [&](auto RB, auto V, dim3 grid, const UpdateArgs &b) {
+        hipLaunchKernelGGL((k_update<T, decltype(RB)::value, decltype(V)::value>), grid, dim3(256), 0, s, b,
+                           t.K, t.pos, t.fix);
+    });
 }
 
 } // namespace recon
 
-hipError_t launch_recon(const ReconArgs &a, size_t nframes, const uint32_t *tab, hipStream_t s) {
+hipError_t launch_recon(const ReconArgs &a, size_t nframes, const DevTable &t, hipStream_t s) {
     if (!a.nrows || !nframes) return hipSuccess;
-    return a.mm <= 8 ? recon::launch<uint8_t>(a, nframes, tab, s) : recon::launch<uint16_t>(a, nframes, tab, s);
+    return a.mm <= 8 ? recon::launch_recon<uint8_t>(a, nframes, t, s) : recon::launch_recon<uint16_t>(a, nframes, t, s);
 }
 
-hipError_t launch_update(const UpdateArgs &a, size_t nframes, const uint32_t *tab, hipStream_t s) {
+hipError_t launch_update(const UpdateArgs &a, size_t nframes, const DevTable &t, hipStream_t s) {
     if (!a.nchg || !nframes) return hipSuccess;
-    return a.mm <= 8 ? recon::ulaunch<uint8_t>(a, nframes, tab, s) : recon::ulaunch<uint16_t>(a, nframes, tab, s);
+    return a.mm <= 8 ? recon::launch_update<uint8_t>(a, nframes, t, s) : recon::launch_update<uint16_t>(a, nframes, t, s);
 }
 
 } // namespace ezrs

@@ -458,91 +458,24 @@ class Codec:
         return out[:n.value].tobytes(), nf.value, rc == 0
 
 
-class Recon:
-    """A reconstruction plan (ezrs_recon_create): one loss pattern shared by every codeword, solved
-    once; ``reconstruct`` rebuilds the lost symbols of interleaved frames in place.  The plan keeps
-    nothing of the codec it was made from.
+class _Plan:
+    """What Recon and Update share: the plan's handle (made by ``_create``, released by the C
+    function named ``_destroy``) and the check of the tensors a plan is applied to."""
 
-    * ``lost``       the lost positions, in the order given (the order of the rebuild rows)
-    * ``survivors``  the surviving positions, ascending
-    * ``nlost``      len(lost); ``result`` entries are nlost or -1"""
-
-    def __init__(self, codec, length, lost):
-        self.lost = [int(p) for p in lost]
-        self.nlost = len(self.lost)
+    def _create(self, create, codec, length, positions):
         self.length, self.nroots, self.device = int(length), codec.nroots, codec.device
         self._w = codec.info.datum_bytes
-        arr = (C.c_uint32 * max(self.nlost, 1))(*self.lost)
+        arr = (C.c_uint32 * max(len(positions), 1))(*positions)
         h = _vp()
         self._h = None
-        _check(lib().ezrs_recon_create(C.byref(h), codec._h, self.length, arr, self.nlost),
-               "ezrs_recon_create")
-        self._h = h
-        gone = set(self.lost)
-        self.survivors = [p for p in range(self.length + self.nroots) if p not in gone]
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                lib().ezrs_recon_destroy(h)
-            except Exception:
-                pass
-            self._h = None
-
-    def reconstruct(self, frames, result=None, stream=None):
-        """frames: [nframes, length + nroots, depth] device tensor as in Codec.encode_interleaved;
-        the lost symbols of every codeword are overwritten, nothing else.  result: an int32 device
-        tensor [nframes * depth] (frame-major) that receives nlost, or -1 where the survivors are
-        not consistent with any codeword; None: no check.  Returns result."""
-        if not getattr(frames, "is_cuda", False):
-            raise EzrsError("frames: expected a GPU tensor")
-        if frames.device.index != self.device:
-            raise EzrsError(f"frames: tensor on cuda:{frames.device.index}, plan on cuda:{self.device}")
-        if frames.element_size() != self._w:
-            raise EzrsError(f"frames: expected {self._w}-byte elements, got {frames.dtype}")
-        if frames.dim() != 3 or (frames.shape[2] > 1 and frames.stride(2) != 1):
-            raise EzrsError("frames: expected a 3-D tensor [nframes, len + nroots, depth] with a "
-                            "contiguous last dimension")
-        nframes, nsym, depth = frames.shape
-        if nsym != self.length + self.nroots or depth == 0:
-            raise EzrsError(f"frames: {nsym} symbols per codeword, the plan has "
-                            f"{self.length + self.nroots}, and a depth of at least 1")
-        if result is not None:
-            _dev_rows(result, "result", self.device, 4, ndim=1)
-            if result.shape[0] < nframes * depth:
-                raise EzrsError("result: fewer entries than codewords")
-        _check(lib().ezrs_reconstruct_interleaved(
-            self._h, _tp(frames), frames.stride(0), frames.stride(1), depth, nframes, _tp(result),
-            _stream_ptr(stream)), "ezrs_reconstruct_interleaved")
-        return result
-
-
-class Update:
-    """A parity-update plan (ezrs_update_create): one set of changed data positions shared by every
-    codeword; ``apply`` XORs G[:, changed]·(new ^ old) into the parity of interleaved frames where it
-    lies and stores the new data symbols.  The plan keeps nothing of the codec it was made from.
-
-    * ``changed``   the changed data positions, in the order given (the order of ``newsyms``' rows)
-    * ``nchanged``  len(changed)"""
-
-    def __init__(self, codec, length, changed):
-        self.changed = [int(p) for p in changed]
-        self.nchanged = len(self.changed)
-        self.length, self.nroots, self.device = int(length), codec.nroots, codec.device
-        self._w = codec.info.datum_bytes
-        arr = (C.c_uint32 * max(self.nchanged, 1))(*self.changed)
-        h = _vp()
-        self._h = None
-        _check(lib().ezrs_update_create(C.byref(h), codec._h, self.length, arr, self.nchanged),
-               "ezrs_update_create")
+        _check(getattr(lib(), create)(C.byref(h), codec._h, self.length, arr, len(positions)), create)
         self._h = h
 
     def __del__(self):
         h = getattr(self, "_h", None)
         if h:
             try:
-                lib().ezrs_update_destroy(h)
+                getattr(lib(), self._destroy)(h)
             except Exception:
                 pass
             self._h = None
@@ -560,6 +493,57 @@ class Update:
         if t.shape[1] != nsym or t.shape[2] == 0:
             raise EzrsError(f"{what}: {t.shape[1]} symbols per codeword, the plan has {nsym}, and a "
                             "depth of at least 1")
+
+
+class Recon(_Plan):
+    """A reconstruction plan (ezrs_recon_create): one loss pattern shared by every codeword, solved
+    once; ``reconstruct`` rebuilds the lost symbols of interleaved frames in place.  The plan keeps
+    nothing of the codec it was made from.
+
+    * ``lost``       the lost positions, in the order given (the order of the rebuild rows)
+    * ``survivors``  the surviving positions, ascending
+    * ``nlost``      len(lost); ``result`` entries are nlost or -1"""
+
+    _destroy = "ezrs_recon_destroy"
+
+    def __init__(self, codec, length, lost):
+        self.lost = [int(p) for p in lost]
+        self.nlost = len(self.lost)
+        self._create("ezrs_recon_create", codec, length, self.lost)
+        gone = set(self.lost)
+        self.survivors = [p for p in range(self.length + self.nroots) if p not in gone]
+
+    def reconstruct(self, frames, result=None, stream=None):
+        """frames: [nframes, length + nroots, depth] device tensor as in Codec.encode_interleaved;
+        the lost symbols of every codeword are overwritten, nothing else.  result: an int32 device
+        tensor [nframes * depth] (frame-major) that receives nlost, or -1 where the survivors are
+        not consistent with any codeword; None: no check.  Returns result."""
+        self._sym_rows(frames, "frames", self.length + self.nroots, "[nframes, len + nroots, depth]")
+        nframes, _, depth = frames.shape
+        if result is not None:
+            _dev_rows(result, "result", self.device, 4, ndim=1)
+            if result.shape[0] < nframes * depth:
+                raise EzrsError("result: fewer entries than codewords")
+        _check(lib().ezrs_reconstruct_interleaved(
+            self._h, _tp(frames), frames.stride(0), frames.stride(1), depth, nframes, _tp(result),
+            _stream_ptr(stream)), "ezrs_reconstruct_interleaved")
+        return result
+
+
+class Update(_Plan):
+    """A parity-update plan (ezrs_update_create): one set of changed data positions shared by every
+    codeword; ``apply`` XORs G[:, changed]·(new ^ old) into the parity of interleaved frames where it
+    lies and stores the new data symbols.  The plan keeps nothing of the codec it was made from.
+
+    * ``changed``   the changed data positions, in the order given (the order of ``newsyms``' rows)
+    * ``nchanged``  len(changed)"""
+
+    _destroy = "ezrs_update_destroy"
+
+    def __init__(self, codec, length, changed):
+        self.changed = [int(p) for p in changed]
+        self.nchanged = len(self.changed)
+        self._create("ezrs_update_create", codec, length, self.changed)
 
     def apply(self, frames, newsyms, stream=None):
         """frames: [nframes, length + nroots, depth] device tensor as in Codec.encode_interleaved;
