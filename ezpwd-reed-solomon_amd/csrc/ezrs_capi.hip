@@ -64,12 +64,14 @@ struct FramePlan {
 // A reconstruction plan: one loss pattern of one codec and length.
 struct ezrs_recon : FramePlan {
     unsigned nlost = 0, nsurv = 0;
+    std::vector<uint32_t> surv, lost;   // host copies of the table's position lists (the pointer form)
 };
 
 // A parity-update plan: one set of changed data positions of one codec and length.  Its table has
 // survivors = changed, lost = the parity positions.
 struct ezrs_update : FramePlan {
     unsigned nchg = 0;
+    std::vector<uint32_t> chg;          // host copy of the changed positions (the pointer form)
 };
 
 namespace {
@@ -763,14 +765,16 @@ int ezrs_recon_create(ezrs_recon **out, const ezrs_codec *c, unsigned len, const
     }
     const unsigned NR = m.spec.nroots, nsurv = len + NR - nlost;
     ezrs_recon *p = new (std::nothrow) ezrs_recon;
+    std::vector<uint32_t> surv;
     const int r = init_plan(p, c, len, "reconstruction", nsurv, nlost, [&](std::vector<uint32_t> &tab) {
         std::vector<uint16_t> cols;
-        std::vector<uint32_t> surv;
         if (!recon_build(m, len, lost, nlost, cols, surv)) return false;
         recon_table(m.spec.mm, NR, cols, surv, lost, nlost, tab);
+        p->lost.assign(lost, lost + nlost);
         return true;
     });
     if (r) return r;
+    p->surv.swap(surv);
     p->nlost = nlost;
     p->nsurv = nsurv;
     *out = p;
@@ -811,7 +815,8 @@ int ezrs_update_create(ezrs_update **out, const ezrs_codec *c, unsigned len, con
         if (!update_build(m, len, changed, nchanged, cols)) return false;
         std::vector<uint32_t> par(NR);
         for (unsigned i = 0; i < NR; ++i) par[i] = len + i;
-        recon_table(m.spec.mm, NR, cols, std::vector<uint32_t>(changed, changed + nchanged), par.data(), NR, tab);
+        p->chg.assign(changed, changed + nchanged);
+        recon_table(m.spec.mm, NR, cols, p->chg, par.data(), NR, tab);
         return true;
     });
     if (r) return r;
@@ -834,6 +839,97 @@ int ezrs_update_interleaved(const ezrs_update *p, void *frames, size_t frame_pit
                  p->nchg, p->len, p->nroots, p->mm, recon_row_pad(p->nroots)};
     const DevTable t = table_view<const uint32_t>(p->d_tab, p->mm, p->nroots, p->nchg, p->nroots);
     hipError_t e = launch_update(a, nframes, t, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "update launch");
+    return 0;
+}
+
+// ---- pointer-array forms: one stripe, every shard a buffer of its own -----------------------------
+namespace {
+
+// The buffers of one pointer-form call: [lo, hi) byte ranges, the written ones first.
+struct PtrRanges {
+    std::pair<uintptr_t, uintptr_t> r[kPtrsMax];
+    unsigned n = 0, nwritten = 0;
+    size_t al = 0;                                  // OR of the addresses
+    void add(const void *p, size_t bytes) {
+        r[n++] = {(uintptr_t)p, (uintptr_t)p + bytes};
+        al |= (size_t)(uintptr_t)p;
+    }
+    // true if a written buffer overlaps any other buffer
+    bool clash() const {
+        for (unsigned i = 0; i < nwritten; ++i)
+            for (unsigned k = i + 1; k < n; ++k)
+                if (r[i].first < r[k].second && r[k].first < r[i].second) return true;
+        return false;
+    }
+};
+
+int ptrs_fail(const char *what) {
+    g_last_error = what;
+    return -EINVAL;
+}
+
+} // namespace
+
+int ezrs_reconstruct_ptrs(const ezrs_recon *p, void *const *shards, size_t shard_len, int32_t *result,
+                          void *stream) {
+    if (!p || !shards) return -EINVAL;
+    if (p->nsurv + p->nlost > kPtrsMax) {
+        g_last_error = "reconstruct_ptrs: len + NROOTS above EZRS_PTRS_MAX pointers";
+        return -ENOTSUP;
+    }
+    if (shard_len == 0) return 0;
+    const size_t w = p->mm <= 8 ? 1 : 2;
+    if (shard_len > SIZE_MAX / w) return -EINVAL;
+    ReconPtrArgs a{{{nullptr, 0, 0, shard_len, 0, 0, 0, 0}, result, p->nsurv, p->nlost, p->mm,
+                    recon_row_pad(p->nroots), result ? p->nroots : p->nlost}, {}};
+    PtrRanges rg;
+    for (unsigned r = 0; r < p->nlost; ++r)         // the written buffers first
+        if ((a.tab.p[p->nsurv + r] = shards[p->lost[r]])) rg.add(shards[p->lost[r]], shard_len * w);
+    rg.nwritten = rg.n;
+    for (unsigned c = 0; c < p->nsurv; ++c) {
+        if (!(a.tab.p[c] = shards[p->surv[c]])) return ptrs_fail("reconstruct_ptrs: a surviving shard is NULL");
+        rg.add(shards[p->surv[c]], shard_len * w);
+    }
+    if (rg.clash()) return ptrs_fail("reconstruct_ptrs: a rebuilt shard's buffer overlaps another buffer");
+    DeviceGuard g(p->device);
+    const DevTable t = table_view<const uint32_t>(p->d_tab, p->mm, p->nroots, p->nsurv, p->nlost);
+    hipError_t e = launch_recon(a, rg.al, t, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "reconstruction launch");
+    return 0;
+}
+
+int ezrs_update_ptrs(const ezrs_update *p, void *const *shards, const void *const *newsyms, size_t shard_len,
+                     void *stream) {
+    if (!p || !shards || !newsyms) return -EINVAL;
+    if ((size_t)2 * p->nchg + p->nroots > kPtrsMax) {
+        g_last_error = "update_ptrs: 2*nchanged + NROOTS above EZRS_PTRS_MAX pointers";
+        return -ENOTSUP;
+    }
+    if (shard_len == 0) return 0;
+    const size_t w = p->mm <= 8 ? 1 : 2;
+    if (shard_len > SIZE_MAX / w) return -EINVAL;
+    UpdatePtrArgs a{{{nullptr, 0, 0, shard_len, 0, 0, 0, 0}, nullptr, 0, 0, p->nchg, p->len, p->nroots, p->mm,
+                     recon_row_pad(p->nroots)}, {}};
+    PtrRanges rg;
+    for (unsigned c = 0; c < p->nchg; ++c) {        // written: the changed shards and the parity
+        if (!(a.tab.p[c] = shards[p->chg[c]])) return ptrs_fail("update_ptrs: a changed shard is NULL");
+        rg.add(shards[p->chg[c]], shard_len * w);
+    }
+    for (unsigned i = 0; i < p->nroots; ++i) {
+        if (!(a.tab.p[p->nchg + i] = shards[p->len + i])) return ptrs_fail("update_ptrs: a parity shard is NULL");
+        rg.add(shards[p->len + i], shard_len * w);
+    }
+    rg.nwritten = rg.n;
+    for (unsigned c = 0; c < p->nchg; ++c) {
+        if (!newsyms[c]) return ptrs_fail("update_ptrs: a newsyms buffer is NULL");
+        a.tab.p[p->nchg + p->nroots + c] = const_cast<void *>(newsyms[c]);
+        rg.add(newsyms[c], shard_len * w);
+    }
+    if (rg.clash()) return ptrs_fail("update_ptrs: a changed or parity shard's buffer overlaps another buffer");
+    DeviceGuard g(p->device);
+    const DevTable t = table_view<const uint32_t>(p->d_tab, p->mm, p->nroots, p->nchg, p->nroots);
+    hipError_t e = launch_update(a, rg.al, t, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return hip_fail(e, "update launch");
     return 0;
 }

@@ -9,6 +9,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "../../include/ezrs.h"
 #include "ezrs_field.hpp"
 
 namespace ezrs {
@@ -258,8 +259,27 @@ struct UpdateArgs {
     unsigned nchg, len, nroots, mm;
     unsigned nrp;                 // recon_row_pad(nroots)
 };
-// t: the plan's device table (table_view of its base).
+// The pointer forms (ezrs_reconstruct_ptrs / ezrs_update_ptrs): one frame whose symbol rows are
+// buffers of their own.  The device pointers travel by value with the kernel arguments, compacted
+// on the host in the order the kernels walk them, so that no position list is read on the device:
+//   reconstruction  survivor c [nsurv] | lost[r] [nlost] (null: that rebuilt row is not stored)
+//   update          changed[c] [nchg] | parity row i [nroots] | new symbols of changed[c] [nchg]
+// span.frames is null and span.sym_stride 0; span.depth is the shard length.
+constexpr unsigned kPtrsMax = EZRS_PTRS_MAX;
+struct PtrTable {
+    void *p[kPtrsMax];
+};
+struct ReconPtrArgs : ReconArgs {
+    PtrTable tab;
+};
+struct UpdatePtrArgs : UpdateArgs {
+    PtrTable tab;
+};
+// t: the plan's device table (table_view of its base).  The pointer forms: al is the OR of the
+// addresses in a.tab that the call uses.
 hipError_t launch_recon(const ReconArgs &a, size_t nframes, const DevTable &t, hipStream_t s);
 hipError_t launch_update(const UpdateArgs &a, size_t nframes, const DevTable &t, hipStream_t s);
+hipError_t launch_recon(const ReconPtrArgs &a, size_t al, const DevTable &t, hipStream_t s);
+hipError_t launch_update(const UpdatePtrArgs &a, size_t al, const DevTable &t, hipStream_t s);
 
 } // namespace ezrs

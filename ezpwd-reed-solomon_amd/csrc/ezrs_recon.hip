@@ -35,6 +35,10 @@
 // The in-place parity update (ezrs_update_create / ezrs_update_interleaved, k_update) is the same
 // machinery on the difference of a few data symbols: the columns of the all-parity matrix at the
 // changed positions, applied to new ^ old and XOR-ed into the parity where it lies.
+//
+// Both kernels address their symbol rows through a compile-time policy (At): rows at one stride from
+// one base (the interleaved calls), or one pointer per row, carried by value in the kernel arguments
+// (ezrs_reconstruct_ptrs / ezrs_update_ptrs: one stripe whose shards are buffers of their own).
 #include <algorithm>
 #include <cerrno>
 #include <new>
@@ -263,6 +267,67 @@ __device__ __forceinline__ void lane(const FrameSpan &a, size_t t, unsigned epl,
     j = a.j0 + q * epl;
 }
 
+// Where the symbol rows of a lane's run are: the addressing policy of both kernels, chosen by the
+// argument struct A.  Strided (ReconArgs, UpdateArgs): the row at position p is p * sym_stride
+// elements past `base`, codeword j of frame f.  Table (ReconPtrArgs, UpdatePtrArgs): one frame, and
+// the row is entry e of the pointer table in the kernel arguments, plus j; e is wave-uniform, so
+// the pointer comes through a scalar load of the kernarg segment.  Callers name a row both ways and
+// the policy takes the one it uses: the position loads of the table form fall away unused.
+template <class A>
+constexpr bool kTable = std::is_same_v<A, ReconPtrArgs> || std::is_same_v<A, UpdatePtrArgs>;
+
+template <typename T, class A>
+struct At {
+    static constexpr bool TABLE = kTable<A>;
+    const A &a;
+    size_t f, j;
+    T *base;                                        // strided only
+    __device__ __forceinline__ At(const A &a, size_t t, unsigned epl) : a(a) {
+        if constexpr (TABLE) {
+            f = 0;
+            j = a.span.j0 + t * epl;
+            base = nullptr;
+        } else {
+            lane(a.span, t, epl, f, j);
+            base = static_cast<T *>(a.span.frames) + f * a.span.frame_pitch + j;
+        }
+    }
+    // Entry e of the table, read where the kernel arguments lie: `a` is the kernels' first argument
+    // and the table its last member.  (Indexed as a.tab.p[e], the two largest k_update forms, u16
+    // with 32 rows at V = 1 and 0, got a copy of the whole argument struct in scratch, 2680 bytes,
+    // and read their pointers from there with vector addresses.)
+    __device__ __forceinline__ T *entry(unsigned e) const {
+        typedef __attribute__((address_space(4))) const char Arg;
+        typedef T *Ptr;                             // a generic pointer that lies in the kernarg segment
+        typedef __attribute__((address_space(4))) const Ptr Ent;
+        static_assert(alignof(A) == alignof(PtrTable), "the table ends A with no padding after it");
+        Arg *const args = (Arg *)__builtin_amdgcn_kernarg_segment_ptr();
+        return ((Ent *)(args + (sizeof(A) - sizeof(PtrTable))))[e];
+    }
+    // the symbol row at position pos, table entry e
+    __device__ __forceinline__ T *row(size_t pos, unsigned e) const {
+        if constexpr (TABLE) return entry(e) + j;
+        else return base + pos * a.span.sym_stride;
+    }
+    // k_update: the first parity row (strided), parity row r from there, the new symbols of changed[c]
+    __device__ __forceinline__ T *parity0() const {
+        if constexpr (TABLE) return nullptr;
+        else return base + (size_t)a.len * a.span.sym_stride;
+    }
+    __device__ __forceinline__ T *parity(T *par, unsigned r) const {
+        if constexpr (TABLE) return entry(a.nchg + r) + j;
+        else return par + (size_t)r * a.span.sym_stride;
+    }
+    __device__ __forceinline__ const T *fresh0() const {
+        if constexpr (TABLE) return nullptr;
+        else return static_cast<const T *>(a.newsyms) + f * a.new_frame_pitch + j;
+    }
+    __device__ __forceinline__ const T *fresh(const T *nbase, unsigned c) const {
+        if constexpr (TABLE) return entry(a.nchg + a.nroots + c) + j;
+        else return nbase + (size_t)c * a.new_sym_stride;
+    }
+};
+
 // One survivor's dwords x into the accumulators of a row block; kp: its columns, bit b at
 // kp + b * nrp.  MB: the symbol bits when known at compile time (the bit loop is then unrolled and
 // the columns' scalar loads are issued ahead), else 0 and mm is used.
@@ -379,11 +444,12 @@ __device__ __forceinline__ void apply8x2(const uint32_t (&x)[ND], const uint32_t
 
 // All survivors of the lane's run into the accumulators of the row block that starts at row r0:
 // kUnroll survivors' loads are issued together, the ragged end goes one by one.
-template <typename T, int RB, int V, int MB>
-__device__ __forceinline__ void sweep(const ReconArgs &a, const T *base, const uint32_t *__restrict__ K,
+template <typename T, int RB, int V, int MB, class A>
+__device__ __forceinline__ void sweep(const At<T, A> &at, const uint32_t *__restrict__ K,
                                       unsigned r0, const uint32_t *__restrict__ surv,
                                       uint32_t (&acc)[RB][Run<T, V>::ND]) {
     using R = Run<T, V>;
+    const A &a = at.a;
     constexpr int ND = R::ND;
     constexpr bool BYTES = sizeof(T) == 1;
     const unsigned mm = MB ? MB : a.mm;
@@ -397,7 +463,7 @@ __device__ __forceinline__ void sweep(const ReconArgs &a, const T *base, const u
     for (; c + kUnroll <= a.nsurv; c += kUnroll) {
         uint32_t x[kUnroll][ND];
 #pragma unroll
-        for (unsigned u = 0; u < kUnroll; ++u) R::load(base + (size_t)surv[c + u] * a.span.sym_stride, x[u]);
+        for (unsigned u = 0; u < kUnroll; ++u) R::load(at.row(surv[c + u], c + u), x[u]);
         if constexpr (BYTES && MB == 8) {
 #pragma unroll
             for (unsigned u = 0; u < kUnroll; u += 2)
@@ -409,14 +475,14 @@ __device__ __forceinline__ void sweep(const ReconArgs &a, const T *base, const u
     }
     for (; c < a.nsurv; ++c) {
         uint32_t x[ND];
-        R::load(base + (size_t)surv[c] * a.span.sym_stride, x);
+        R::load(at.row(surv[c], c), x);
         one(x, c);
     }
 }
 
 // K: the coefficients; surv / lost: the positions; fix: [nrp] (recon_table).
-template <typename T, int RB, int V>
-__global__ void __launch_bounds__(256) k_recon(ReconArgs a, const uint32_t *__restrict__ K,
+template <typename T, int RB, int V, class A>
+__global__ void __launch_bounds__(256) k_recon(A a, const uint32_t *__restrict__ K,
                                                const uint32_t *__restrict__ surv,
                                                const uint32_t *__restrict__ lost,
                                                const uint32_t *__restrict__ fix) {
@@ -425,9 +491,7 @@ __global__ void __launch_bounds__(256) k_recon(ReconArgs a, const uint32_t *__re
     constexpr unsigned W = 8 * sizeof(T);
     const size_t t = lane_index();
     if (t >= a.span.runs * a.span.nf) return;
-    size_t f, j;
-    lane(a.span, t, R::EPL, f, j);
-    T *const base = static_cast<T *>(a.span.frames) + f * a.span.frame_pitch + j;
+    const At<T, A> at(a, t, R::EPL);
     uint32_t bad[ND];
 #pragma unroll
     for (int d = 0; d < ND; ++d) bad[d] = 0;
@@ -437,8 +501,8 @@ __global__ void __launch_bounds__(256) k_recon(ReconArgs a, const uint32_t *__re
         for (int r = 0; r < RB; ++r)
 #pragma unroll
             for (int d = 0; d < ND; ++d) acc[r][d] = 0;
-        if (a.mm == 8) sweep<T, RB, V, 8>(a, base, K, r0, surv, acc);
-        else sweep<T, RB, V, 0>(a, base, K, r0, surv, acc);
+        if (a.mm == 8) sweep<T, RB, V, 8>(at, K, r0, surv, acc);
+        else sweep<T, RB, V, 0>(at, K, r0, surv, acc);
 #pragma unroll
         for (int r = 0; r < RB; ++r) {
             const unsigned row = r0 + r;
@@ -446,7 +510,11 @@ __global__ void __launch_bounds__(256) k_recon(ReconArgs a, const uint32_t *__re
 #pragma unroll
             for (int d = 0; d < ND; ++d) acc[r][d] ^= fx;
             if (row < a.nlost) {
-                R::store(base + (size_t)lost[row] * a.span.sym_stride, acc[r]);
+                if constexpr (kTable<A>) {          // a null entry: that shard is not wanted
+                    if (at.entry(a.nsurv + row)) R::store(at.row(0, a.nsurv + row), acc[r]);
+                } else {
+                    R::store(at.row(lost[row], 0), acc[r]);
+                }
             } else {                                // check rows; the padding rows are zero
 #pragma unroll
                 for (int d = 0; d < ND; ++d) bad[d] |= acc[r][d];
@@ -454,7 +522,7 @@ __global__ void __launch_bounds__(256) k_recon(ReconArgs a, const uint32_t *__re
         }
     }
     if (a.result) {
-        int32_t *res = a.result + f * a.span.depth + j;
+        int32_t *res = a.result + at.f * a.span.depth + at.j;
         constexpr unsigned EPD = V ? 4 / sizeof(T) : 1;
 #pragma unroll
         for (int d = 0; d < ND; ++d)
@@ -475,15 +543,15 @@ __global__ void __launch_bounds__(256) k_recon(ReconArgs a, const uint32_t *__re
 // symbols, and so is `fix`).
 
 // N changed positions from c0: the old and the new symbols, loaded together; d = old ^ new.
-template <typename T, int V, int N>
-__device__ __forceinline__ void udelta(const UpdateArgs &a, const T *base, const T *nbase,
+template <typename T, int V, int N, class A>
+__device__ __forceinline__ void udelta(const At<T, A> &at, const T *nbase,
                                        const uint32_t *__restrict__ chg, unsigned c0,
                                        uint32_t (&d)[N][Run<T, V>::ND], uint32_t (&nw)[N][Run<T, V>::ND]) {
     using R = Run<T, V>;
 #pragma unroll
     for (int u = 0; u < N; ++u) {
-        R::load(base + (size_t)chg[c0 + u] * a.span.sym_stride, d[u]);
-        R::load(nbase + (size_t)(c0 + u) * a.new_sym_stride, nw[u]);
+        R::load(at.row(chg[c0 + u], c0 + u), d[u]);
+        R::load(at.fresh(nbase, c0 + u), nw[u]);
     }
 #pragma unroll
     for (int u = 0; u < N; ++u)
@@ -527,24 +595,25 @@ constexpr unsigned ukeep(int accs) { return accs >= 128 ? 1 : accs >= 64 ? 2 : k
 
 // One row block.  NC != 0: the plan's NC deltas are in d.  NC == 0: all changed positions are read
 // (again), a group's loads issued together, the ragged end one by one.
-template <typename T, int RB, int V, int MB, int NC>
-__device__ __forceinline__ void usweep(const UpdateArgs &a, const T *base, const T *nbase,
+template <typename T, int RB, int V, int MB, int NC, class A>
+__device__ __forceinline__ void usweep(const At<T, A> &at, const T *nbase,
                                        const uint32_t *__restrict__ chg, const uint32_t *__restrict__ K,
                                        const uint32_t (&d)[NC ? NC : 1][Run<T, V>::ND],
                                        uint32_t (&acc)[RB][Run<T, V>::ND]) {
     constexpr int ND = Run<T, V>::ND, G = ugroup(RB * ND);
+    const A &a = at.a;
     if constexpr (NC != 0) {
         ufeed<T, RB, V, MB, NC>(a, K, 0, d, acc);
     } else {
         unsigned c = 0;
         for (; c + G <= a.nchg; c += G) {
             uint32_t e[G][ND], w[G][ND];
-            udelta<T, V, G>(a, base, nbase, chg, c, e, w);
+            udelta<T, V, G>(at, nbase, chg, c, e, w);
             ufeed<T, RB, V, MB, G>(a, K, c, e, acc);
         }
         for (; c < a.nchg; ++c) {
             uint32_t e[1][ND], w[1][ND];
-            udelta<T, V, 1>(a, base, nbase, chg, c, e, w);
+            udelta<T, V, 1>(at, nbase, chg, c, e, w);
             ufeed<T, RB, V, MB, 1>(a, K, c, e, acc);
         }
     }
@@ -556,15 +625,16 @@ __device__ __forceinline__ void usweep(const UpdateArgs &a, const T *base, const
 // (Deltas kept across several blocks are not built: the compiler then hoists every bit mask and
 // selector of every delta out of the block loop and the kernels need 160 - 256 VGPRs.)  Either way
 // the data is overwritten only after the last block.
-template <typename T, int RB, int V, int NC>
-__device__ __forceinline__ void ubody(const UpdateArgs &a, const uint32_t *__restrict__ K,
+template <typename T, int RB, int V, int NC, class A>
+__device__ __forceinline__ void ubody(const At<T, A> &at, const uint32_t *__restrict__ K,
                                       const uint32_t *__restrict__ chg, const uint32_t *__restrict__ fix,
-                                      T *base, const T *nbase) {
+                                      const T *nbase) {
     using R = Run<T, V>;
     constexpr int ND = R::ND;
-    T *const par = base + (size_t)a.len * a.span.sym_stride;
+    const A &a = at.a;
+    T *const par = at.parity0();
     uint32_t d[NC ? NC : 1][ND], nw[NC ? NC : 1][ND];
-    if constexpr (NC != 0) udelta<T, V, NC>(a, base, nbase, chg, 0, d, nw);
+    if constexpr (NC != 0) udelta<T, V, NC>(at, nbase, chg, 0, d, nw);
     auto block = [&](unsigned r0) {
         uint32_t acc[RB][ND];
         if constexpr (uearly(RB * ND)) {
@@ -575,7 +645,7 @@ __device__ __forceinline__ void ubody(const UpdateArgs &a, const uint32_t *__res
 #pragma unroll
             for (int r = 0; r < RB; ++r) {
                 const unsigned row = r0 + r < a.nroots ? r0 + r : a.nroots - 1;
-                R::load(par + (size_t)row * a.span.sym_stride, acc[r]);
+                R::load(at.parity(par, row), acc[r]);
             }
         } else {
 #pragma unroll
@@ -584,12 +654,12 @@ __device__ __forceinline__ void ubody(const UpdateArgs &a, const uint32_t *__res
                 for (int i = 0; i < ND; ++i) acc[r][i] = 0;
         }
         const uint32_t *const Kb = K + (sizeof(T) == 1 ? 2 * r0 : r0);
-        if (a.mm == 8) usweep<T, RB, V, 8, NC>(a, base, nbase, chg, Kb, d, acc);
-        else usweep<T, RB, V, 0, NC>(a, base, nbase, chg, Kb, d, acc);
+        if (a.mm == 8) usweep<T, RB, V, 8, NC>(at, nbase, chg, Kb, d, acc);
+        else usweep<T, RB, V, 0, NC>(at, nbase, chg, Kb, d, acc);
 #pragma unroll
         for (int r = 0; r < RB; ++r)
             if (r0 + r < a.nroots) {
-                T *const p = par + (size_t)(r0 + r) * a.span.sym_stride;
+                T *const p = at.parity(par, r0 + r);
                 const uint32_t fx = fix[r0 + r];
                 if constexpr (uearly(RB * ND)) {
 #pragma unroll
@@ -606,42 +676,40 @@ __device__ __forceinline__ void ubody(const UpdateArgs &a, const uint32_t *__res
     if constexpr (NC != 0) {
         block(0);
 #pragma unroll
-        for (int u = 0; u < NC; ++u) R::store(base + (size_t)chg[u] * a.span.sym_stride, nw[u]);
+        for (int u = 0; u < NC; ++u) R::store(at.row(chg[u], u), nw[u]);
     } else {
         for (unsigned r0 = 0; r0 < a.nroots; r0 += RB) block(r0);
         for (unsigned c = 0; c < a.nchg; ++c) {
             uint32_t x[ND];
-            R::load(nbase + (size_t)c * a.new_sym_stride, x);
-            R::store(base + (size_t)chg[c] * a.span.sym_stride, x);
+            R::load(at.fresh(nbase, c), x);
+            R::store(at.row(chg[c], c), x);
         }
     }
 }
 
 // K: the coefficients of the changed positions; chg: the positions; fix: [nrp] (recon_table).
-template <typename T, int RB, int V>
-__global__ void __launch_bounds__(256) k_update(UpdateArgs a, const uint32_t *__restrict__ K,
+template <typename T, int RB, int V, class A>
+__global__ void __launch_bounds__(256) k_update(A a, const uint32_t *__restrict__ K,
                                                 const uint32_t *__restrict__ chg,
                                                 const uint32_t *__restrict__ fix) {
     using R = Run<T, V>;
     const size_t t = lane_index();
     if (t >= a.span.runs * a.span.nf) return;
-    size_t f, j;
-    lane(a.span, t, R::EPL, f, j);
-    T *const base = static_cast<T *>(a.span.frames) + f * a.span.frame_pitch + j;
-    const T *const nbase = static_cast<const T *>(a.newsyms) + f * a.new_frame_pitch + j;
+    const At<T, A> at(a, t, R::EPL);
+    const T *const nbase = at.fresh0();
     static_assert(kUnroll == 4, "one case per count of changed positions kept in registers");
     constexpr unsigned KEEP = ukeep(RB * R::ND);
     const unsigned nc = a.nroots <= RB && a.nchg <= KEEP ? a.nchg : 0;
     if (nc == 1) {
-        ubody<T, RB, V, 1>(a, K, chg, fix, base, nbase);
+        ubody<T, RB, V, 1>(at, K, chg, fix, nbase);
     } else if (nc == 2) {
-        if constexpr (KEEP >= 2) ubody<T, RB, V, 2>(a, K, chg, fix, base, nbase);
+        if constexpr (KEEP >= 2) ubody<T, RB, V, 2>(at, K, chg, fix, nbase);
     } else if (nc == 3) {
-        if constexpr (KEEP >= 4) ubody<T, RB, V, 3>(a, K, chg, fix, base, nbase);
+        if constexpr (KEEP >= 4) ubody<T, RB, V, 3>(at, K, chg, fix, nbase);
     } else if (nc == 4) {
-        if constexpr (KEEP >= 4) ubody<T, RB, V, 4>(a, K, chg, fix, base, nbase);
+        if constexpr (KEEP >= 4) ubody<T, RB, V, 4>(at, K, chg, fix, nbase);
     } else {
-        ubody<T, RB, V, 0>(a, K, chg, fix, base, nbase);
+        ubody<T, RB, V, 0>(at, K, chg, fix, nbase);
     }
 }
 
@@ -712,37 +780,60 @@ static hipError_t launch_frames(A a, size_t nframes, unsigned rb, size_t al, F &
     return e;
 }
 
-template <typename T>
-static hipError_t launch_recon(const ReconArgs &a, size_t nframes, const DevTable &t, hipStream_t s) {
-    return launch_frames<T>(a, nframes, rows_per_block<T>(a.nrows), 0,
-                            [&](auto RB, auto V, dim3 grid, const ReconArgs &b) {
-        hipLaunchKernelGGL((k_recon<T, decltype(RB)::value, decltype(V)::value>), grid, dim3(256), 0, s, b,
+// A: the addressing; al: the OR of the addresses the table form uses (0 for the strided form, whose
+// frames and strides launch_frames looks at itself)
+template <typename T, class A>
+static hipError_t launch_recon(const A &a, size_t nframes, size_t al, const DevTable &t, hipStream_t s) {
+    return launch_frames<T>(a, nframes, rows_per_block<T>(a.nrows), al,
+                            [&](auto RB, auto V, dim3 grid, const A &b) {
+        hipLaunchKernelGGL((k_recon<T, decltype(RB)::value, decltype(V)::value, A>), grid, dim3(256), 0, s, b,
                            t.K, t.pos, t.lost, t.fix);
     });
 }
 
-template <typename T>
-static hipError_t launch_update(const UpdateArgs &a, size_t nframes, const DevTable &t, hipStream_t s) {
-    // `newsyms` is accessed like the frames
-    size_t al = (size_t)(uintptr_t)a.newsyms | a.new_sym_stride * sizeof(T);
+template <typename T, class A>
+static hipError_t launch_update(const A &a, size_t nframes, size_t al, const DevTable &t, hipStream_t s) {
+    // `newsyms` is accessed like the frames (null and 0 in the table form)
+    al |= (size_t)(uintptr_t)a.newsyms | a.new_sym_stride * sizeof(T);
     if (nframes > 1) al |= a.new_frame_pitch * sizeof(T);
     return launch_frames<T>(a, nframes, rows_per_block<T>(a.nroots), al,
-                            [&](auto RB, auto V, dim3 grid, const UpdateArgs &b) {
-        hipLaunchKernelGGL((k_update<T, decltype(RB)::value, decltype(V)::value>), grid, dim3(256), 0, s, b,
+                            [&](auto RB, auto V, dim3 grid, const A &b) {
+        hipLaunchKernelGGL((k_update<T, decltype(RB)::value, decltype(V)::value, A>), grid, dim3(256), 0, s, b,
                            t.K, t.pos, t.fix);
     });
 }
 
 } // namespace recon
 
-hipError_t launch_recon(const ReconArgs &a, size_t nframes, const DevTable &t, hipStream_t s) {
+namespace {
+
+template <class A>
+hipError_t recon_any(const A &a, size_t nframes, size_t al, const DevTable &t, hipStream_t s) {
     if (!a.nrows || !nframes) return hipSuccess;
-    return a.mm <= 8 ? recon::launch_recon<uint8_t>(a, nframes, t, s) : recon::launch_recon<uint16_t>(a, nframes, t, s);
+    return a.mm <= 8 ? recon::launch_recon<uint8_t>(a, nframes, al, t, s)
+                     : recon::launch_recon<uint16_t>(a, nframes, al, t, s);
 }
 
-hipError_t launch_update(const UpdateArgs &a, size_t nframes, const DevTable &t, hipStream_t s) {
+template <class A>
+hipError_t update_any(const A &a, size_t nframes, size_t al, const DevTable &t, hipStream_t s) {
     if (!a.nchg || !nframes) return hipSuccess;
-    return a.mm <= 8 ? recon::launch_update<uint8_t>(a, nframes, t, s) : recon::launch_update<uint16_t>(a, nframes, t, s);
+    return a.mm <= 8 ? recon::launch_update<uint8_t>(a, nframes, al, t, s)
+                     : recon::launch_update<uint16_t>(a, nframes, al, t, s);
+}
+
+} // namespace
+
+hipError_t launch_recon(const ReconArgs &a, size_t nframes, const DevTable &t, hipStream_t s) {
+    return recon_any(a, nframes, 0, t, s);
+}
+hipError_t launch_update(const UpdateArgs &a, size_t nframes, const DevTable &t, hipStream_t s) {
+    return update_any(a, nframes, 0, t, s);
+}
+hipError_t launch_recon(const ReconPtrArgs &a, size_t al, const DevTable &t, hipStream_t s) {
+    return recon_any(a, 1, al, t, s);
+}
+hipError_t launch_update(const UpdatePtrArgs &a, size_t al, const DevTable &t, hipStream_t s) {
+    return update_any(a, 1, al, t, s);
 }
 
 } // namespace ezrs

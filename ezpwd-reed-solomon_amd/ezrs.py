@@ -108,6 +108,8 @@ def lib():
         L.ezrs_update_destroy.argtypes = [_vp]
         L.ezrs_update_interleaved.argtypes = [_vp, _vp, _sz, _sz, _sz, _sz, _vp, _sz, _sz, _vp]
         L.ezrs_update_bitmatrix.argtypes = [_u, _u, _u, _u, _u, _i, _u, _vp, _u, _vp, _sz]
+        L.ezrs_reconstruct_ptrs.argtypes = [_vp, _vp, _sz, _vp, _vp]
+        L.ezrs_update_ptrs.argtypes = [_vp, _vp, _vp, _sz, _vp]
         L.ezrs_kernel_path.argtypes = [_vp]
         L.ezrs_set_launch_rows.argtypes = [_vp, _sz]
         L.ezrs_set_semantics.argtypes = [_vp, _i]
@@ -494,6 +496,33 @@ class _Plan:
             raise EzrsError(f"{what}: {t.shape[1]} symbols per codeword, the plan has {nsym}, and a "
                             "depth of at least 1")
 
+    def _shard_ptrs(self, seq, what, n, optional, shard_len=None):
+        """Validate a sequence of n 1-D contiguous device tensors of one length (None allowed at the
+        indices in `optional`); returns (host array of their device pointers, that length)."""
+        seq = list(seq)
+        if len(seq) != n:
+            raise EzrsError(f"{what}: {len(seq)} entries, the plan has {n}")
+        arr = (C.c_void_p * max(n, 1))()
+        for i, t in enumerate(seq):
+            if t is None:
+                if i not in optional:
+                    raise EzrsError(f"{what}[{i}]: None where the call needs a buffer")
+                continue
+            if not getattr(t, "is_cuda", False):
+                raise EzrsError(f"{what}[{i}]: expected a GPU tensor")
+            if t.device.index != self.device:
+                raise EzrsError(f"{what}[{i}]: tensor on cuda:{t.device.index}, plan on cuda:{self.device}")
+            if t.element_size() != self._w:
+                raise EzrsError(f"{what}[{i}]: expected {self._w}-byte elements, got {t.dtype}")
+            if t.dim() != 1 or (t.shape[0] > 1 and t.stride(0) != 1):
+                raise EzrsError(f"{what}[{i}]: expected a 1-D contiguous tensor")
+            if shard_len is None:
+                shard_len = t.shape[0]
+            elif t.shape[0] != shard_len:
+                raise EzrsError(f"{what}[{i}]: {t.shape[0]} symbols, the other shards have {shard_len}")
+            arr[i] = t.data_ptr()
+        return arr, (0 if shard_len is None else shard_len)
+
 
 class Recon(_Plan):
     """A reconstruction plan (ezrs_recon_create): one loss pattern shared by every codeword, solved
@@ -529,6 +558,21 @@ class Recon(_Plan):
             _stream_ptr(stream)), "ezrs_reconstruct_interleaved")
         return result
 
+    def reconstruct_ptrs(self, shards, result=None, stream=None):
+        """The pointer form (ezrs_reconstruct_ptrs): one stripe, every shard a tensor of its own.
+        shards: length + nroots 1-D contiguous device tensors of equal length, by position; the
+        survivors are only read, the tensors at the lost positions receive the rebuilt shards, and
+        None there (and only there) means that shard is not wanted.  result: as in ``reconstruct``,
+        one entry per symbol of a shard.  Returns result."""
+        arr, n = self._shard_ptrs(shards, "shards", self.length + self.nroots, set(self.lost))
+        if result is not None:
+            _dev_rows(result, "result", self.device, 4, ndim=1)
+            if result.shape[0] < n:
+                raise EzrsError("result: fewer entries than codewords")
+        _check(lib().ezrs_reconstruct_ptrs(self._h, arr, n, _tp(result), _stream_ptr(stream)),
+               "ezrs_reconstruct_ptrs")
+        return result
+
 
 class Update(_Plan):
     """A parity-update plan (ezrs_update_create): one set of changed data positions shared by every
@@ -560,6 +604,19 @@ class Update(_Plan):
         _check(lib().ezrs_update_interleaved(
             self._h, _tp(frames), frames.stride(0), frames.stride(1), depth, nframes, _tp(newsyms),
             newsyms.stride(0), newsyms.stride(1), _stream_ptr(stream)), "ezrs_update_interleaved")
+
+    def apply_ptrs(self, shards, newsyms, stream=None):
+        """The pointer form (ezrs_update_ptrs): one stripe, every shard a tensor of its own.
+        shards: length + nroots entries by position, of which only the changed and the parity
+        positions are used (1-D contiguous device tensors of equal length); every other entry may be
+        None: those shards need not be on the device.  newsyms: nchanged such tensors, in the order
+        of ``changed``, only read; they must not overlap the changed and parity shards."""
+        S = self.length + self.nroots
+        used = set(self.changed) | set(range(self.length, S))
+        shards = [t if i in used else None for i, t in enumerate(shards)]   # the others are ignored
+        arr, n = self._shard_ptrs(shards, "shards", S, set(range(S)) - used)
+        new, _ = self._shard_ptrs(newsyms, "newsyms", self.nchanged, (), n)
+        _check(lib().ezrs_update_ptrs(self._h, arr, new, n, _stream_ptr(stream)), "ezrs_update_ptrs")
 
 
 def update_bitmatrix(params, length, changed):

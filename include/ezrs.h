@@ -325,6 +325,44 @@ int ezrs_update_bitmatrix(unsigned symbol_bits, unsigned poly, unsigned fcr, uns
                           unsigned nroots, int dual, unsigned len, const uint32_t *changed,
                           unsigned nchanged, uint16_t *cols, size_t cols_cap);
 
+/* Pointer-array forms of the two calls above (device-resident): one stripe whose shards are
+ * buffers of their own, as erasure-coding callers have them (ISA-L's ec_encode_data(len, k, rows,
+ * tbls, data**, coding**), jerasure), instead of one base pointer and one sym_stride.  shard_len is
+ * what depth is in the strided calls: codeword j is symbol j of every shard, in elements of the
+ * datum.  `shards` (and `newsyms`) are HOST arrays of DEVICE pointers; they are read during the call
+ * and not kept: the pointers travel with the kernel arguments, so the caller may free or overwrite
+ * the arrays as soon as the call returns, although the work is asynchronous.  One stripe per call;
+ * never allocate, never synchronise, no workspace; capturable like the strided forms.  For every
+ * valid input the bytes written and `result` equal what the strided call produces on the same
+ * symbols.  Accesses are 16 bytes wide per lane when every pointer the call uses is a multiple of
+ * 16, 4 bytes when of 4, else one element; any alignment of the datum is valid.
+ *   ezrs_reconstruct_ptrs   shards[len + NROOTS], indexed by position.  The entry of a surviving
+ *            position is that shard, shard_len symbols, only read.  The entry of a lost position is
+ *            where that rebuilt shard goes; NULL there means "not wanted" (a degraded read that needs
+ *            one shard): nothing is written for it (its row is computed with the others and
+ *            dropped), and `result` is not affected, since the check rows depend on the survivors
+ *            only.  result: nullable int32[shard_len], as in ezrs_reconstruct_interleaved.  An
+ *            nlost == 0 plan is a verify that writes nothing to any shard; the all-parity plan
+ *            (lost = len..len+NROOTS-1) is the pointer-form encode.
+ *   ezrs_update_ptrs        shards[len + NROOTS], indexed by position; only the entries at the
+ *            plan's changed positions and at the parity positions len..len+NROOTS-1 are used, every
+ *            other entry is ignored and may be NULL: those shards need not be on the device.
+ *            newsyms[nchanged], in the order of `changed`, each shard_len new symbols, only read.
+ *            Per codeword exactly ezrs_update_interleaved: the old parity is read, not recomputed;
+ *            the data is overwritten after the parity; bits above the symbol as there.
+ * Checked on the host before any launch.  -EINVAL: null plan, `shards` or `newsyms`; a NULL entry
+ * the call must read or write (a survivor; a changed, parity or newsyms buffer); shard_len *
+ * datum bytes overflowing size_t; two written buffers that overlap over [p, p + shard_len * datum
+ * bytes), or a written buffer that overlaps a read one.  -ENOTSUP: the call uses more than
+ * EZRS_PTRS_MAX pointers: len + NROOTS for the reconstruction, 2*nchanged + NROOTS for the update
+ * (every codec of up to 8 bits fits at any length, wider codecs when shortened).  shard_len == 0
+ * returns 0 and touches nothing. */
+#define EZRS_PTRS_MAX 320   /* device pointers one *_ptrs call can carry (they travel as kernel arguments) */
+int ezrs_reconstruct_ptrs(const ezrs_recon *plan, void *const *shards, size_t shard_len,
+                          int32_t *result, void *stream);
+int ezrs_update_ptrs(const ezrs_update *plan, void *const *shards, const void *const *newsyms,
+                     size_t shard_len, void *stream);
+
 /* Host-memory forms: the same contracts with HOST pointers.  The batch is streamed through the
  * device in chunks of `chunk` codewords (0 = library default) over two HIP streams with
  * asynchronous copies; pinned host memory (ezrs_host_alloc) gets full PCIe overlap.  Blocking:

@@ -4,6 +4,7 @@ per-codeword check) against the staged decode given the same erasures in every c
 (Codec.decode_interleaved), on the same buffers.
 
     python tools/recon_bench.py [--gib 1.0] [--out profiles/recon/recon_bench.json]
+    python tools/recon_bench.py --ptrs [--gib 1.0] [--out profiles/recon/recon_ptrs_bench.json]
 
 One frame per shape: len + nroots shards of `depth` symbols, symbol stride = depth, sized so that
 the frame holds at least --gib GiB (well past the 256 MiB Infinity Cache).  Device events; every
@@ -13,7 +14,16 @@ that each figure has at least 0.5 s of timed work; the figure is the median, the
 find them already rebuilt, which changes nothing in what either path computes (the staged decode
 runs its erasure path on every codeword that carries erasures, the reconstruction never reads the
 lost shards).  GB/s counts the frame's bytes once; hbm_fraction counts survivor bytes read + lost
-bytes written + result bytes against 8 TB/s."""
+bytes written + result bytes against 8 TB/s.
+
+--ptrs: the pointer form (ezrs_reconstruct_ptrs) against the strided form instead, same shapes and
+the same data, every shard of the pointer form an allocation of its own; the calls alternate in the
+same process as above.  The pointer form is called through the C ABI with its pointer array built
+once, as a C caller has it; ptrs_over_strided is the ratio of the medians.  A third figure,
+ptrs_inframe, is the pointer form on pointers to the rows of the strided frame itself: the same
+addresses as the strided form, so that the kernels' addressing is compared apart from where the
+allocator put the shards."""
+import ctypes as C
 import argparse
 import json
 import os
@@ -66,12 +76,73 @@ def figure(fns):
                 "iters": iters[n]} for n, v in runs.items()}
 
 
+def main_ptrs(args):
+    L, sp = ezrs.lib(), ezrs._stream_ptr(None)
+    out = {"gib": args.gib, "reps": REPS, "device": torch.cuda.get_device_name(0), "results": []}
+    for name, mk, length, lost in SHAPES:
+        c = mk()
+        S, nlost = length + c.nroots, len(lost)
+        depth = (int(args.gib * (1 << 30)) // S + 1023) // 1024 * 1024
+        g = torch.Generator(device="cuda").manual_seed(1)
+        shards = torch.empty((S, depth), dtype=torch.uint8, device="cuda")
+        for s in range(length):
+            shards[s] = torch.randint(0, 256, (depth,), generator=g, device="cuda", dtype=torch.int32).to(torch.uint8)
+        frames = shards[None]
+        c.encode_interleaved(frames)
+        good = shards[lost].clone()
+        own = [shards[s].clone() for s in range(S)]             # every shard an allocation of its own
+        arr = (C.c_void_p * S)(*[t.data_ptr() for t in own])
+        arr_in = (C.c_void_p * S)(*[shards[s].data_ptr() for s in range(S)])
+        plan = c.recon_plan(length, lost)
+        res, res_p = (torch.empty(depth, dtype=torch.int32, device="cuda") for _ in range(2))
+        rp = C.c_void_p(res_p.data_ptr())
+        fns = {"strided": lambda: plan.reconstruct(frames, result=res),
+               "ptrs": lambda: L.ezrs_reconstruct_ptrs(plan._h, arr, depth, rp, sp),
+               "strided_nocheck": lambda: plan.reconstruct(frames),
+               "ptrs_nocheck": lambda: L.ezrs_reconstruct_ptrs(plan._h, arr, depth, None, sp),
+               "ptrs_inframe": lambda: L.ezrs_reconstruct_ptrs(plan._h, arr_in, depth, rp, sp),
+               "ptrs_inframe_nocheck": lambda: L.ezrs_reconstruct_ptrs(plan._h, arr_in, depth, None, sp)}
+        for what, fn in fns.items():                # each path once on garbage
+            shards[lost] = 0x5A
+            for p in lost:
+                own[p].fill_(0x5A)
+            r = fn()
+            assert r is None or r is res or r == 0, (name, what)
+            torch.cuda.synchronize()
+            got = torch.stack([own[p] for p in lost]) if what in ("ptrs", "ptrs_nocheck") else shards[lost]
+            assert torch.equal(got, good), (name, what)
+        assert torch.equal(res, res_p) and bool((res == nlost).all()), name
+        fg = figure(fns)
+        torch.cuda.synchronize()
+        assert torch.equal(torch.stack([own[p] for p in lost]), good), name
+        rec = {"shape": name, "len": length, "nroots": c.nroots, "nlost": nlost, "depth": depth,
+               "frame_bytes": S * depth}
+        for k, v in fg.items():
+            rec[f"t_{k}_ms"], rec[f"spread_{k}"] = v["median_s"] * 1e3, v["spread"]
+        rec["ptrs_over_strided"] = fg["ptrs"]["median_s"] / fg["strided"]["median_s"]
+        rec["ptrs_over_strided_nocheck"] = fg["ptrs_nocheck"]["median_s"] / fg["strided_nocheck"]["median_s"]
+        rec["inframe_over_strided"] = fg["ptrs_inframe"]["median_s"] / fg["strided"]["median_s"]
+        rec["inframe_over_strided_nocheck"] = (fg["ptrs_inframe_nocheck"]["median_s"] /
+                                               fg["strided_nocheck"]["median_s"])
+        rec["iters"] = {k: v["iters"] for k, v in fg.items()}
+        out["results"].append(rec)
+        print(json.dumps(rec), flush=True)
+        del shards, frames, good, own, res, res_p, plan, c, fns
+        torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gib", type=float, default=1.0)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "recon", "recon_bench.json"))
+    ap.add_argument("--ptrs", action="store_true", help="the pointer form against the strided form")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    args.out = args.out or os.path.join(ROOT, "profiles", "recon",
+                                        "recon_ptrs_bench.json" if args.ptrs else "recon_bench.json")
     torch.cuda.set_device(0)
+    if args.ptrs:
+        return write(args.out, main_ptrs(args))
     out = {"gib": args.gib, "reps": REPS, "device": torch.cuda.get_device_name(0), "results": []}
     for name, mk, length, lost in SHAPES:
         c = mk()
@@ -124,10 +195,14 @@ def main():
         print(json.dumps(rec), flush=True)
         del shards, frames, good, eras, neras, res, res_d, plan, c
         torch.cuda.empty_cache()
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as f:
+    write(args.out, out)
+
+
+def write(path, out):
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "w") as f:
         json.dump(out, f, indent=1)
-    print("wrote", args.out)
+    print("wrote", path)
 
 
 if __name__ == "__main__":

@@ -5,6 +5,7 @@ re-encode the project has) and the staged Codec.encode_interleaved, on the same 
 comparison shares a kernel with the update.
 
     python tools/update_bench.py [--gib 1.0] [--out profiles/update/update_bench.json]
+    python tools/update_bench.py --ptrs [--gib 1.0] [--out profiles/update/update_ptrs_bench.json]
 
 One frame per shape: len + nroots shards of `depth` symbols, symbol stride = depth, sized so that
 the frame holds at least --gib GiB (well past the 256 MiB Infinity Cache); newsyms is a packed
@@ -14,7 +15,16 @@ the figure is the median, the spread (max - min) / median.  Repeats of the updat
 symbols already in place (a zero delta), which changes nothing in what it loads, computes or
 stores.  GB/s counts the frame's bytes once; hbm_fraction counts the bytes the update must move
 (old and new changed symbols and the parity read, changed symbols and parity written) against
-8 TB/s."""
+8 TB/s.
+
+--ptrs: the pointer form (ezrs_update_ptrs) against the strided form instead, same shapes and the
+same data; the pointer form has only the changed shards, the parity shards and the new symbols,
+each an allocation of its own.  The calls alternate in the same process as above; the pointer form
+is called through the C ABI with its pointer arrays built once, as a C caller has them;
+ptrs_over_strided is the ratio of the medians.  A third figure, ptrs_inframe, is the pointer form on
+pointers to the rows of the strided frame and of its newsyms: the same addresses as the strided
+form, so that the kernels' addressing is compared apart from where the allocator put the shards."""
+import ctypes as C
 import argparse
 import json
 import os
@@ -77,12 +87,64 @@ def rand_rows(rows, depth, w, mask, g):
     return out
 
 
+def main_ptrs(args):
+    L, sp = ezrs.lib(), ezrs._stream_ptr(None)
+    out = {"gib": args.gib, "reps": REPS, "device": torch.cuda.get_device_name(0), "results": []}
+    for name, mk, length, changed in SHAPES:
+        c = mk()
+        w, NR, nchg = c.info.datum_bytes, c.nroots, len(changed)
+        S = length + NR
+        depth = (int(args.gib * (1 << 30)) // (S * w) + 1023) // 1024 * 1024
+        g = torch.Generator(device="cuda").manual_seed(1)
+        shards = torch.empty((S, depth), dtype=torch.uint8 if w == 1 else torch.int16, device="cuda")
+        shards[:length] = rand_rows(length, depth, w, c.nn, g)
+        frames = shards[None]
+        parity = list(range(length, S))
+        plan = c.update_plan(length, changed)
+        c.recon_plan(length, parity).reconstruct(frames)        # the first parity
+        newsyms = rand_rows(nchg, depth, w, c.nn, g)[None]
+        used = changed + parity
+        own = {p: shards[p].clone() for p in used}              # only what the call needs, each its own
+        new = [newsyms[0, r].clone() for r in range(nchg)]
+        arr = (C.c_void_p * S)(*[own[p].data_ptr() if p in own else None for p in range(S)])
+        narr = (C.c_void_p * nchg)(*[t.data_ptr() for t in new])
+        arr_in = (C.c_void_p * S)(*[shards[p].data_ptr() if p in own else None for p in range(S)])
+        narr_in = (C.c_void_p * nchg)(*[newsyms[0, r].data_ptr() for r in range(nchg)])
+        fns = {"strided": lambda: plan.apply(frames, newsyms),
+               "ptrs": lambda: L.ezrs_update_ptrs(plan._h, arr, narr, depth, sp),
+               "ptrs_inframe": lambda: L.ezrs_update_ptrs(plan._h, arr_in, narr_in, depth, sp)}
+        for what, fn in fns.items():                # each path once, a nonzero delta
+            assert fn() in (0, None), (name, what)
+        torch.cuda.synchronize()
+        assert torch.equal(torch.stack([own[p] for p in used]), shards[used]), name
+        fg = figure(fns)
+        torch.cuda.synchronize()
+        assert torch.equal(torch.stack([own[p] for p in used]), shards[used]), name
+        rec = {"shape": name, "len": length, "nroots": NR, "nchanged": nchg, "depth": depth,
+               "frame_bytes": S * depth * w, "update_bytes_moved": (3 * nchg + 2 * NR) * depth * w}
+        for k, v in fg.items():
+            rec[f"t_{k}_ms"], rec[f"spread_{k}"] = v["median_s"] * 1e3, v["spread"]
+        rec["ptrs_over_strided"] = fg["ptrs"]["median_s"] / fg["strided"]["median_s"]
+        rec["inframe_over_strided"] = fg["ptrs_inframe"]["median_s"] / fg["strided"]["median_s"]
+        rec["iters"] = {k: v["iters"] for k, v in fg.items()}
+        out["results"].append(rec)
+        print(json.dumps(rec), flush=True)
+        del shards, frames, own, new, newsyms, plan, c, fns
+        torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gib", type=float, default=1.0)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "update", "update_bench.json"))
+    ap.add_argument("--ptrs", action="store_true", help="the pointer form against the strided form")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    args.out = args.out or os.path.join(ROOT, "profiles", "update",
+                                        "update_ptrs_bench.json" if args.ptrs else "update_bench.json")
     torch.cuda.set_device(0)
+    if args.ptrs:
+        return write(args.out, main_ptrs(args))
     out = {"gib": args.gib, "reps": REPS, "device": torch.cuda.get_device_name(0), "results": []}
     for name, mk, length, changed in SHAPES:
         c = mk()
@@ -136,10 +198,14 @@ def main():
         print(json.dumps(rec), flush=True)
         del shards, frames, good, old, newsyms, plan, reenc, c
         torch.cuda.empty_cache()
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as f:
+    write(args.out, out)
+
+
+def write(path, out):
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "w") as f:
         json.dump(out, f, indent=1)
-    print("wrote", args.out)
+    print("wrote", path)
 
 
 if __name__ == "__main__":
