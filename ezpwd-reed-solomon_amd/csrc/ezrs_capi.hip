@@ -934,6 +934,64 @@ int ezrs_update_ptrs(const ezrs_update *p, void *const *shards, const void *cons
     return 0;
 }
 
+// ---- batched pointer forms: many stripes, the pointers in a table on the device --------------------
+namespace {
+
+// What the host can check of a batch call: the table is on the device.  w: bytes of the datum;
+// 0: go on, 1: nothing to do, else the error.
+int batch_check(const char *call, size_t pitch, size_t need, size_t shard_len, size_t nstripes,
+                unsigned align, size_t w) {
+    const char *bad = nullptr;
+    if (pitch < need) bad = "table_pitch below len + NROOTS";
+    else if (align != 16 && align != 4 && align != w) bad = "align is not 16, 4 or the datum size";
+    else if (shard_len > SIZE_MAX / w) bad = "shard_len * datum bytes overflows size_t";
+    else if (shard_len && nstripes > SIZE_MAX / shard_len) bad = "nstripes * shard_len overflows size_t";
+    if (bad) {
+        g_last_error = std::string(call) + ": " + bad;
+        return -EINVAL;
+    }
+    return nstripes && shard_len ? 0 : 1;
+}
+
+} // namespace
+
+int ezrs_reconstruct_ptrs_batch(const ezrs_recon *p, void *const *table, size_t table_pitch, size_t shard_len,
+                                size_t nstripes, unsigned align, int32_t *result, void *stream) {
+    if (!p || !table) return -EINVAL;
+    const size_t w = p->mm <= 8 ? 1 : 2;
+    if (int r = batch_check("reconstruct_ptrs_batch", table_pitch, (size_t)p->len + p->nroots, shard_len,
+                            nstripes, align, w))
+        return r < 0 ? r : 0;
+    ReconBatchArgs a{{{nullptr, 0, 0, shard_len, 0, 0, 0, 0}, result, p->nsurv, p->nlost, p->mm,
+                      recon_row_pad(p->nroots), result ? p->nroots : p->nlost}, table, table_pitch, 0};
+    DeviceGuard g(p->device);
+    const DevTable t = table_view<const uint32_t>(p->d_tab, p->mm, p->nroots, p->nsurv, p->nlost);
+    hipError_t e = launch_recon(a, nstripes, align, t, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "reconstruction launch");
+    return 0;
+}
+
+int ezrs_update_ptrs_batch(const ezrs_update *p, void *const *table, size_t table_pitch,
+                           const void *const *new_table, size_t new_pitch, size_t shard_len, size_t nstripes,
+                           unsigned align, void *stream) {
+    if (!p || !table || !new_table) return -EINVAL;
+    const size_t w = p->mm <= 8 ? 1 : 2;
+    if (new_pitch < p->nchg) {
+        g_last_error = "update_ptrs_batch: new_pitch below nchanged";
+        return -EINVAL;
+    }
+    if (int r = batch_check("update_ptrs_batch", table_pitch, (size_t)p->len + p->nroots, shard_len,
+                            nstripes, align, w))
+        return r < 0 ? r : 0;
+    UpdateBatchArgs a{{{nullptr, 0, 0, shard_len, 0, 0, 0, 0}, nullptr, 0, 0, p->nchg, p->len, p->nroots, p->mm,
+                       recon_row_pad(p->nroots)}, table, new_table, table_pitch, new_pitch, 0};
+    DeviceGuard g(p->device);
+    const DevTable t = table_view<const uint32_t>(p->d_tab, p->mm, p->nroots, p->nchg, p->nroots);
+    hipError_t e = launch_update(a, nstripes, align, t, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "update launch");
+    return 0;
+}
+
 int ezrs_update_bitmatrix(unsigned symbol_bits, unsigned poly, unsigned fcr, unsigned prim, unsigned nroots,
                           int dual, unsigned len, const uint32_t *changed, unsigned nchanged, uint16_t *cols,
                           size_t cols_cap) {

@@ -275,11 +275,29 @@ struct ReconPtrArgs : ReconArgs {
 struct UpdatePtrArgs : UpdateArgs {
     PtrTable tab;
 };
+// The batched pointer forms (ezrs_reconstruct_ptrs_batch / ezrs_update_ptrs_batch): nstripes frames
+// whose symbol rows are buffers of their own, named by a pointer table in DEVICE memory that the
+// kernels read while they run: the row at position p of stripe s is table[s * pitch + p], by
+// position and not compacted, and the new symbols of changed[r] are new_table[s * new_pitch + r].
+// span.frames is null, span.sym_stride and span.frame_pitch 0; span.depth is the shard length.
+// wruns: the threads a stripe takes, span.runs rounded up to a wave, set per launch by the launcher.
+struct ReconBatchArgs : ReconArgs {
+    void *const *table;
+    size_t pitch, wruns;
+};
+struct UpdateBatchArgs : UpdateArgs {
+    void *const *table;
+    const void *const *new_table;
+    size_t pitch, new_pitch, wruns;
+};
 // t: the plan's device table (table_view of its base).  The pointer forms: al is the OR of the
-// addresses in a.tab that the call uses.
+// addresses in a.tab that the call uses; the batched forms: the alignment the caller promises for
+// every pointer of the tables.
 hipError_t launch_recon(const ReconArgs &a, size_t nframes, const DevTable &t, hipStream_t s);
 hipError_t launch_update(const UpdateArgs &a, size_t nframes, const DevTable &t, hipStream_t s);
 hipError_t launch_recon(const ReconPtrArgs &a, size_t al, const DevTable &t, hipStream_t s);
 hipError_t launch_update(const UpdatePtrArgs &a, size_t al, const DevTable &t, hipStream_t s);
+hipError_t launch_recon(const ReconBatchArgs &a, size_t nstripes, size_t al, const DevTable &t, hipStream_t s);
+hipError_t launch_update(const UpdateBatchArgs &a, size_t nstripes, size_t al, const DevTable &t, hipStream_t s);
 
 } // namespace ezrs

@@ -37,8 +37,10 @@
 // changed positions, applied to new ^ old and XOR-ed into the parity where it lies.
 //
 // Both kernels address their symbol rows through a compile-time policy (At): rows at one stride from
-// one base (the interleaved calls), or one pointer per row, carried by value in the kernel arguments
-// (ezrs_reconstruct_ptrs / ezrs_update_ptrs: one stripe whose shards are buffers of their own).
+// one base (the interleaved calls), one pointer per row, carried by value in the kernel arguments
+// (ezrs_reconstruct_ptrs / ezrs_update_ptrs: one stripe whose shards are buffers of their own), or
+// one pointer per row and stripe in a table in device memory (ezrs_reconstruct_ptrs_batch /
+// ezrs_update_ptrs_batch: many such stripes per call).
 #include <algorithm>
 #include <cerrno>
 #include <new>
@@ -273,17 +275,61 @@ __device__ __forceinline__ void lane(const FrameSpan &a, size_t t, unsigned epl,
 // the row is entry e of the pointer table in the kernel arguments, plus j; e is wave-uniform, so
 // the pointer comes through a scalar load of the kernarg segment.  Callers name a row both ways and
 // the policy takes the one it uses: the position loads of the table form fall away unused.
+// Batch (ReconBatchArgs, UpdateBatchArgs): the row at position p of stripe f is entry f * pitch + p
+// of a pointer table in device memory, plus j.  The stripe is uniform over a wave (batch_lane), the
+// position is a wave-uniform scalar load from the plan's table, and the table is read through the
+// constant address space (nothing the call writes may overlap it), so the pointer is one more
+// scalar load, dependent on the position's, and never a vector load.
 template <class A>
 constexpr bool kTable = std::is_same_v<A, ReconPtrArgs> || std::is_same_v<A, UpdatePtrArgs>;
+template <class A>
+constexpr bool kBatch = std::is_same_v<A, ReconBatchArgs> || std::is_same_v<A, UpdateBatchArgs>;
+
+// The lane map of the batch forms.  A stripe takes a.wruns threads, its runs rounded up to a wave,
+// so a wave never spans two stripes: wave w of the launch works on stripe s = w / (wruns / 64) of
+// the launch (f = f0 + s), and its lane l on run q = (w % (wruns / 64)) * 64 + l.  w is built from
+// scalars only and s goes through readfirstlane, so the compiler knows what follows from s to be
+// uniform: the stripe's table row and every pointer fetched from it.  false: no run for this
+// thread, past the stripe's runs or past the launch's stripes (s stays below 2^32: launch_frames).
+template <class A>
+__device__ __forceinline__ bool batch_lane(const A &a, unsigned epl, size_t &f, size_t &j) {
+    const uint32_t wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const size_t w = (size_t)blockIdx.x * 4 + wid, wps = a.wruns >> 6;
+    uint32_t s, r;                                  // stripe of the launch, wave of the stripe
+    if (((w | wps) >> 32) == 0) {                   // 32-bit division, as in lane()
+        s = (uint32_t)w / (uint32_t)wps;
+        r = (uint32_t)w - s * (uint32_t)wps;
+    } else {
+        s = (uint32_t)(w / wps);
+        r = (uint32_t)(w - (size_t)s * wps);
+    }
+    s = __builtin_amdgcn_readfirstlane(s);
+    r = __builtin_amdgcn_readfirstlane(r);
+    const size_t q = (size_t)r * 64 + (threadIdx.x & 63);
+    f = a.span.f0 + s;
+    j = a.span.j0 + q * epl;
+    return s < a.span.nf && q < a.span.runs;
+}
 
 template <typename T, class A>
 struct At {
-    static constexpr bool TABLE = kTable<A>;
+    static constexpr bool TABLE = kTable<A>, BATCH = kBatch<A>;
+    typedef T *Row;
+    typedef __attribute__((address_space(4))) const Row Slot;  // a generic pointer in constant memory
     const A &a;
     size_t f, j;
     T *base;                                        // strided only
+    Slot *trow, *nrow;                              // batch only: the stripe's rows of the two tables
+    bool live;                                      // batch only: the thread has a run
     __device__ __forceinline__ At(const A &a, size_t t, unsigned epl) : a(a) {
-        if constexpr (TABLE) {
+        trow = nrow = nullptr;
+        live = true;
+        if constexpr (BATCH) {
+            live = batch_lane(a, epl, f, j);
+            base = nullptr;
+            trow = (Slot *)a.table + f * a.pitch;
+            if constexpr (std::is_same_v<A, UpdateBatchArgs>) nrow = (Slot *)a.new_table + f * a.new_pitch;
+        } else if constexpr (TABLE) {
             f = 0;
             j = a.span.j0 + t * epl;
             base = nullptr;
@@ -292,6 +338,8 @@ struct At {
             base = static_cast<T *>(a.span.frames) + f * a.span.frame_pitch + j;
         }
     }
+    // batch: the pointer at position pos of the lane's stripe
+    __device__ __forceinline__ T *slot(size_t pos) const { return trow[pos]; }
     // Entry e of the table, read where the kernel arguments lie: `a` is the kernels' first argument
     // and the table its last member.  (Indexed as a.tab.p[e], the two largest k_update forms, u16
     // with 32 rows at V = 1 and 0, got a copy of the whole argument struct in scratch, 2680 bytes,
@@ -306,24 +354,27 @@ struct At {
     }
     // the symbol row at position pos, table entry e
     __device__ __forceinline__ T *row(size_t pos, unsigned e) const {
-        if constexpr (TABLE) return entry(e) + j;
+        if constexpr (BATCH) return slot(pos) + j;
+        else if constexpr (TABLE) return entry(e) + j;
         else return base + pos * a.span.sym_stride;
     }
     // k_update: the first parity row (strided), parity row r from there, the new symbols of changed[c]
     __device__ __forceinline__ T *parity0() const {
-        if constexpr (TABLE) return nullptr;
+        if constexpr (TABLE || BATCH) return nullptr;
         else return base + (size_t)a.len * a.span.sym_stride;
     }
     __device__ __forceinline__ T *parity(T *par, unsigned r) const {
-        if constexpr (TABLE) return entry(a.nchg + r) + j;
+        if constexpr (BATCH) return slot(a.len + r) + j;
+        else if constexpr (TABLE) return entry(a.nchg + r) + j;
         else return par + (size_t)r * a.span.sym_stride;
     }
     __device__ __forceinline__ const T *fresh0() const {
-        if constexpr (TABLE) return nullptr;
+        if constexpr (TABLE || BATCH) return nullptr;
         else return static_cast<const T *>(a.newsyms) + f * a.new_frame_pitch + j;
     }
     __device__ __forceinline__ const T *fresh(const T *nbase, unsigned c) const {
-        if constexpr (TABLE) return entry(a.nchg + a.nroots + c) + j;
+        if constexpr (BATCH) return nrow[c] + j;
+        else if constexpr (TABLE) return entry(a.nchg + a.nroots + c) + j;
         else return nbase + (size_t)c * a.new_sym_stride;
     }
 };
@@ -490,8 +541,11 @@ __global__ void __launch_bounds__(256) k_recon(A a, const uint32_t *__restrict__
     constexpr int ND = R::ND;
     constexpr unsigned W = 8 * sizeof(T);
     const size_t t = lane_index();
-    if (t >= a.span.runs * a.span.nf) return;
+    if constexpr (!kBatch<A>)
+        if (t >= a.span.runs * a.span.nf) return;
     const At<T, A> at(a, t, R::EPL);
+    if constexpr (kBatch<A>)                        // nothing has been asked for yet
+        if (!at.live) return;
     uint32_t bad[ND];
 #pragma unroll
     for (int d = 0; d < ND; ++d) bad[d] = 0;
@@ -512,6 +566,8 @@ __global__ void __launch_bounds__(256) k_recon(A a, const uint32_t *__restrict__
             if (row < a.nlost) {
                 if constexpr (kTable<A>) {          // a null entry: that shard is not wanted
                     if (at.entry(a.nsurv + row)) R::store(at.row(0, a.nsurv + row), acc[r]);
+                } else if constexpr (kBatch<A>) {   // ... by this stripe
+                    if (at.slot(lost[row])) R::store(at.row(lost[row], 0), acc[r]);
                 } else {
                     R::store(at.row(lost[row], 0), acc[r]);
                 }
@@ -694,8 +750,11 @@ __global__ void __launch_bounds__(256) k_update(A a, const uint32_t *__restrict_
                                                 const uint32_t *__restrict__ fix) {
     using R = Run<T, V>;
     const size_t t = lane_index();
-    if (t >= a.span.runs * a.span.nf) return;
+    if constexpr (!kBatch<A>)
+        if (t >= a.span.runs * a.span.nf) return;
     const At<T, A> at(a, t, R::EPL);
+    if constexpr (kBatch<A>)                        // nothing has been asked for yet
+        if (!at.live) return;
     const T *const nbase = at.fresh0();
     static_assert(kUnroll == 4, "one case per count of changed positions kept in registers");
     constexpr unsigned KEEP = ukeep(RB * R::ND);
@@ -739,8 +798,9 @@ static void with_rb(unsigned rb, F &&f) {
 
 // Every codeword of every frame through a frame-in-place kernel.  a: the kernel's arguments, its
 // FrameSpan `span` filled in per launch here; al: what else than the frames has to be aligned for a
-// vector access, OR-ed (addresses and byte strides); kernel(RB, V, grid, a): launches the kernel's
-// <T, RB, V> form.
+// vector access, OR-ed (addresses and byte strides; the batch forms: the alignment promised for the
+// tables' pointers); kernel(RB, V, grid, a): launches the kernel's <T, RB, V> form.  A frame takes
+// one thread per run, in the batch forms rounded up to a wave.
 template <typename T, class A, class F>
 static hipError_t launch_frames(A a, size_t nframes, unsigned rb, size_t al, F &&kernel) {
     FrameSpan &sp = a.span;
@@ -751,11 +811,15 @@ static hipError_t launch_frames(A a, size_t nframes, unsigned rb, size_t al, F &
         sp.runs = n / Run<T, decltype(V)::value>::EPL;
         const size_t maxt = (size_t)1 << 38;        // threads per launch (2^30 workgroups)
         if (sp.runs > maxt) return hipErrorInvalidValue;
-        const size_t fstep = maxt / sp.runs;
+        size_t tpf = sp.runs;                       // threads per frame
+        if constexpr (kBatch<A>) a.wruns = tpf = (sp.runs + 63) / 64 * 64;   // batch_lane
+        size_t fstep = maxt / tpf;
+        if constexpr (kBatch<A>)                    // a launch's stripe index and the few past it: 32 bits
+            if (fstep > (size_t)1 << 31) fstep = (size_t)1 << 31;
         for (size_t f0 = 0; f0 < nframes; f0 += fstep) {
             sp.f0 = f0;
             sp.nf = nframes - f0 < fstep ? nframes - f0 : fstep;
-            const dim3 grid((unsigned)((sp.runs * sp.nf + 255) / 256));
+            const dim3 grid((unsigned)((tpf * sp.nf + 255) / 256));
             with_rb<T>(rb, [&](auto RB) { kernel(RB, V, grid, a); });
             const hipError_t e = hipGetLastError();
             if (e != hipSuccess) return e;
@@ -834,6 +898,12 @@ hipError_t launch_recon(const ReconPtrArgs &a, size_t al, const DevTable &t, hip
 }
 hipError_t launch_update(const UpdatePtrArgs &a, size_t al, const DevTable &t, hipStream_t s) {
     return update_any(a, 1, al, t, s);
+}
+hipError_t launch_recon(const ReconBatchArgs &a, size_t nstripes, size_t al, const DevTable &t, hipStream_t s) {
+    return recon_any(a, nstripes, al, t, s);
+}
+hipError_t launch_update(const UpdateBatchArgs &a, size_t nstripes, size_t al, const DevTable &t, hipStream_t s) {
+    return update_any(a, nstripes, al, t, s);
 }
 
 } // namespace ezrs

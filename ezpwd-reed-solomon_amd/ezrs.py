@@ -110,6 +110,8 @@ def lib():
         L.ezrs_update_bitmatrix.argtypes = [_u, _u, _u, _u, _u, _i, _u, _vp, _u, _vp, _sz]
         L.ezrs_reconstruct_ptrs.argtypes = [_vp, _vp, _sz, _vp, _vp]
         L.ezrs_update_ptrs.argtypes = [_vp, _vp, _vp, _sz, _vp]
+        L.ezrs_reconstruct_ptrs_batch.argtypes = [_vp, _vp, _sz, _sz, _sz, _u, _vp, _vp]
+        L.ezrs_update_ptrs_batch.argtypes = [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _u, _vp]
         L.ezrs_kernel_path.argtypes = [_vp]
         L.ezrs_set_launch_rows.argtypes = [_vp, _sz]
         L.ezrs_set_semantics.argtypes = [_vp, _i]
@@ -524,6 +526,32 @@ class _Plan:
         return arr, (0 if shard_len is None else shard_len)
 
 
+    def _ptr_table(self, t, what, need):
+        """Validate an int64 device tensor [nstripes, pitch >= need] with a contiguous last dimension;
+        returns (nstripes, pitch in entries)."""
+        import torch
+        if not getattr(t, "is_cuda", False):
+            raise EzrsError(f"{what}: expected a GPU tensor")
+        if t.device.index != self.device:
+            raise EzrsError(f"{what}: tensor on cuda:{t.device.index}, plan on cuda:{self.device}")
+        if t.dtype != torch.int64:
+            raise EzrsError(f"{what}: expected int64 entries (device pointers), got {t.dtype}")
+        if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+            raise EzrsError(f"{what}: expected a 2-D tensor [nstripes, pitch] with a contiguous last dimension")
+        if t.shape[1] < need:
+            raise EzrsError(f"{what}: {t.shape[1]} entries per stripe, the plan needs {need}")
+        pitch = t.stride(0) if t.shape[0] > 1 else t.shape[1]
+        if pitch < need:
+            raise EzrsError(f"{what}: a stripe stride of {pitch} entries, the plan needs {need}")
+        return t.shape[0], pitch
+
+    def _align(self, align):
+        align = self._w if align is None else int(align)
+        if align not in (16, 4, self._w):
+            raise EzrsError(f"align: {align}, expected 16, 4 or the datum size {self._w}")
+        return align
+
+
 class Recon(_Plan):
     """A reconstruction plan (ezrs_recon_create): one loss pattern shared by every codeword, solved
     once; ``reconstruct`` rebuilds the lost symbols of interleaved frames in place.  The plan keeps
@@ -574,6 +602,28 @@ class Recon(_Plan):
         return result
 
 
+    def reconstruct_ptrs_batch(self, table, shard_len, align=None, result=None, stream=None):
+        """The batched pointer form (ezrs_reconstruct_ptrs_batch): table is an int64 device tensor
+        [nstripes, pitch >= length + nroots] of device pointers, entry [s, p] the shard at position
+        p of stripe s, shard_len symbols (``ptr_table`` builds one); 0 at a lost position: that
+        stripe does not want that shard.  align: what every pointer is a multiple of, 16, 4 or the
+        datum size (None); a promise, not checked.  The table is read while the kernels run: keep it
+        alive and unchanged until the stream has done the work.  result: an int32 device tensor
+        [nstripes * shard_len], stripe-major, or None.  Returns result."""
+        nstripes, pitch = self._ptr_table(table, "table", self.length + self.nroots)
+        shard_len, align = int(shard_len), self._align(align)
+        if shard_len < 0:
+            raise EzrsError("shard_len: negative")
+        if result is not None:
+            _dev_rows(result, "result", self.device, 4, ndim=1)
+            if result.shape[0] < nstripes * shard_len:
+                raise EzrsError("result: fewer entries than codewords")
+        _check(lib().ezrs_reconstruct_ptrs_batch(self._h, _tp(table), pitch, shard_len, nstripes, align,
+                                                 _tp(result), _stream_ptr(stream)),
+               "ezrs_reconstruct_ptrs_batch")
+        return result
+
+
 class Update(_Plan):
     """A parity-update plan (ezrs_update_create): one set of changed data positions shared by every
     codeword; ``apply`` XORs G[:, changed]·(new ^ old) into the parity of interleaved frames where it
@@ -617,6 +667,71 @@ class Update(_Plan):
         arr, n = self._shard_ptrs(shards, "shards", S, set(range(S)) - used)
         new, _ = self._shard_ptrs(newsyms, "newsyms", self.nchanged, (), n)
         _check(lib().ezrs_update_ptrs(self._h, arr, new, n, _stream_ptr(stream)), "ezrs_update_ptrs")
+
+
+    def apply_ptrs_batch(self, table, new_table, shard_len, align=None, stream=None):
+        """The batched pointer form (ezrs_update_ptrs_batch): table as in
+        ``Recon.reconstruct_ptrs_batch``, of which only the entries at the changed and the parity
+        positions are used; new_table: int64 device tensor [nstripes, pitch >= nchanged], entry
+        [s, r] the new symbols of changed[r] of stripe s.  align: the promise for the pointers of
+        both tables.  Both tables are read while the kernels run."""
+        nstripes, pitch = self._ptr_table(table, "table", self.length + self.nroots)
+        nnew, new_pitch = self._ptr_table(new_table, "new_table", self.nchanged)
+        if nnew != nstripes:
+            raise EzrsError(f"new_table: {nnew} stripes, table has {nstripes}")
+        shard_len, align = int(shard_len), self._align(align)
+        if shard_len < 0:
+            raise EzrsError("shard_len: negative")
+        _check(lib().ezrs_update_ptrs_batch(self._h, _tp(table), pitch, _tp(new_table), new_pitch, shard_len,
+                                            nstripes, align, _stream_ptr(stream)),
+               "ezrs_update_ptrs_batch")
+
+
+def ptr_table(stripes, optional=()):
+    """The pointer table of the batched pointer forms from tensors.  stripes: a sequence of
+    per-stripe sequences (all of one length) of 1-D contiguous device tensors, all on one device,
+    with elements of one size and of one length; None is allowed at the indices in `optional`.
+    Returns (table, shard_len, align): the int64 device tensor [nstripes, entries] of their device
+    pointers (0 for None), their common length, and the largest of 16 / 4 / the element size that
+    every pointer is a multiple of.  The tensors must outlive the use of the table."""
+    import torch
+    stripes = [list(st) for st in stripes]
+    if not stripes or not stripes[0]:
+        raise EzrsError("ptr_table: no stripes, or no entries in a stripe")
+    optional = set(optional)
+    rows, first, bits = [], None, 0
+    for s, st in enumerate(stripes):
+        if len(st) != len(stripes[0]):
+            raise EzrsError(f"ptr_table: stripe {s} has {len(st)} entries, stripe 0 has {len(stripes[0])}")
+        row = []
+        for i, t in enumerate(st):
+            what = f"ptr_table: stripes[{s}][{i}]"
+            if t is None:
+                if i not in optional:
+                    raise EzrsError(f"{what}: None where a buffer is needed")
+                row.append(0)
+                continue
+            if not getattr(t, "is_cuda", False):
+                raise EzrsError(f"{what}: expected a GPU tensor")
+            if t.dim() != 1 or (t.shape[0] > 1 and t.stride(0) != 1):
+                raise EzrsError(f"{what}: expected a 1-D contiguous tensor")
+            if first is None:
+                first = t
+            if t.device != first.device:
+                raise EzrsError(f"{what}: tensor on {t.device}, the others on {first.device}")
+            if t.element_size() != first.element_size():
+                raise EzrsError(f"{what}: {t.element_size()}-byte elements, the others have "
+                                f"{first.element_size()}")
+            if t.shape[0] != first.shape[0]:
+                raise EzrsError(f"{what}: {t.shape[0]} symbols, the other shards have {first.shape[0]}")
+            bits |= t.data_ptr()
+            row.append(t.data_ptr())
+        rows.append(row)
+    if first is None:
+        raise EzrsError("ptr_table: no buffer at all")
+    table = torch.tensor(rows, dtype=torch.int64).to(first.device)
+    align = 16 if bits % 16 == 0 else 4 if bits % 4 == 0 else first.element_size()
+    return table, first.shape[0], align
 
 
 def update_bitmatrix(params, length, changed):

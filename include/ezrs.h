@@ -363,6 +363,53 @@ int ezrs_reconstruct_ptrs(const ezrs_recon *plan, void *const *shards, size_t sh
 int ezrs_update_ptrs(const ezrs_update *plan, void *const *shards, const void *const *newsyms,
                      size_t shard_len, void *stream);
 
+/* Batched pointer-table forms of the two calls above (device-resident): nstripes stripes per call,
+ * every shard of every stripe a buffer of its own, all stripes under the one plan (a rebuild, a
+ * scrub, a flush of small writes).  Per stripe exactly the one-stripe form on that stripe's
+ * pointers: the same bytes written and the same `result`.  What differs is where the pointers are:
+ *   table    a DEVICE array of DEVICE pointers on the plan's device.  table[s*table_pitch + p] is
+ *            the shard at position p (0 .. len+NROOTS-1) of stripe s, shard_len symbols of the datum;
+ *            indexed by position, as `shards` is, and not compacted.  table_pitch >= len + NROOTS;
+ *            the entries from len + NROOTS up to table_pitch are never read.  One table, resident on
+ *            the device, serves a reconstruction plan, a verify plan and an update plan of the same
+ *            stripes with no host work between them.
+ *   new_table   new_table[s*new_pitch + r]: the new symbols of changed[r] of stripe s, shard_len of
+ *            them, only read.  new_pitch >= nchanged; the entries past nchanged are never read.
+ * The kernels read the tables WHILE THEY RUN: unlike the host arrays of the one-stripe forms, the
+ * tables must stay valid and unchanged until the work has completed on `stream`.  There is no limit
+ * on the number of pointers (EZRS_PTRS_MAX does not apply: nothing travels as kernel arguments).
+ * Asynchronous; no workspace; never allocate, never synchronise; capturable.
+ *   ezrs_reconstruct_ptrs_batch   survivors are only read; the entry of a lost position is where
+ *            that rebuilt shard goes, and NULL there means "not wanted" for that stripe only: nothing
+ *            is written for it and `result` is not affected.  result: nullable
+ *            int32[nstripes*shard_len], stripe-major (codeword j of stripe s at s*shard_len + j):
+ *            nlost or -1, as in ezrs_reconstruct_interleaved.  An nlost == 0 plan is a verify that
+ *            writes nothing to any shard; the all-parity plan is the batched pointer-form encode.
+ *   ezrs_update_ptrs_batch        only the entries of `table` at the plan's changed positions and
+ *            at the parity positions len..len+NROOTS-1, and new_table, are used; every other entry is
+ *            ignored and may be NULL or garbage.  The old parity is read, not recomputed; the data is
+ *            overwritten after the parity; bits above the symbol as in ezrs_update_interleaved.
+ *   align    the caller's promise: every pointer the call uses (in both tables) is a multiple of
+ *            `align` bytes.  16, 4 or the size of the datum; it selects the access width, 16 bytes
+ *            per lane, 4 bytes or one element, exactly as the OR of the addresses does in the
+ *            one-stripe forms.  The ragged end of shard_len (what is left after whole 16- or 4-byte
+ *            runs) goes element by element, whatever `align` is.
+ * NOT CHECKED, because the host cannot see the tables, and undefined behaviour when broken: a
+ * pointer that is not a multiple of `align`; a NULL (or invalid) entry that the call must read or
+ * write (a survivor; a changed, parity or new_table entry); any overlap between two buffers the
+ * call writes, in the same stripe or in different stripes, or between a buffer it writes and one
+ * it reads (a table included), each over [p, p + shard_len * datum bytes).
+ * Checked on the host before any launch.  -EINVAL: null plan, `table` or `new_table`; table_pitch <
+ * len + NROOTS; new_pitch < nchanged; align not 16, 4 or the datum size; shard_len * datum bytes or
+ * nstripes * shard_len overflowing size_t.  Otherwise nstripes == 0 or shard_len == 0 returns 0
+ * and touches nothing. */
+int ezrs_reconstruct_ptrs_batch(const ezrs_recon *plan, void *const *table, size_t table_pitch,
+                                size_t shard_len, size_t nstripes, unsigned align, int32_t *result,
+                                void *stream);
+int ezrs_update_ptrs_batch(const ezrs_update *plan, void *const *table, size_t table_pitch,
+                           const void *const *new_table, size_t new_pitch, size_t shard_len,
+                           size_t nstripes, unsigned align, void *stream);
+
 /* Host-memory forms: the same contracts with HOST pointers.  The batch is streamed through the
  * device in chunks of `chunk` codewords (0 = library default) over two HIP streams with
  * asynchronous copies; pinned host memory (ezrs_host_alloc) gets full PCIe overlap.  Blocking:

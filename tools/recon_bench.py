@@ -5,6 +5,7 @@ per-codeword check) against the staged decode given the same erasures in every c
 
     python tools/recon_bench.py [--gib 1.0] [--out profiles/recon/recon_bench.json]
     python tools/recon_bench.py --ptrs [--gib 1.0] [--out profiles/recon/recon_ptrs_bench.json]
+    python tools/recon_bench.py --batch [--gib 1.0] [--out profiles/recon/recon_batch_bench.json]
 
 One frame per shape: len + nroots shards of `depth` symbols, symbol stride = depth, sized so that
 the frame holds at least --gib GiB (well past the 256 MiB Infinity Cache).  Device events; every
@@ -22,7 +23,22 @@ same process as above.  The pointer form is called through the C ABI with its po
 once, as a C caller has it; ptrs_over_strided is the ratio of the medians.  A third figure,
 ptrs_inframe, is the pointer form on pointers to the rows of the strided frame itself: the same
 addresses as the strided form, so that the kernels' addressing is compared apart from where the
-allocator put the shards."""
+allocator put the shards.
+
+--batch: many small stripes under one plan, three ways, alternating in the same process as above.
+Per shape and shard size (4 KiB, 64 KiB, 1 MiB) there are nstripes stripes, so many that all shards
+together hold at least --gib GiB.  Every shard is a buffer of its own in one pool, placed by a random
+permutation, so addresses are monotonic neither in the position nor in the stripe.
+  loop     one ezrs_reconstruct_ptrs call per stripe through the C ABI, the host pointer arrays built
+           once (the Python loop around the calls adds its own share to each of them)
+  batch    one ezrs_reconstruct_ptrs_batch call on the same shards, its table built once by
+           ezrs.ptr_table
+  strided  one ezrs_reconstruct_interleaved call with nframes = nstripes on a frame tensor of the
+           same bytes: the same arithmetic and no pointer fetch
+  batch_inframe  the batch call on a table of pointers to the rows of the strided frames
+           themselves: the same addresses as the strided call, so that the kernels' addressing is
+           compared apart from where the shards lie
+batch_over_loop, batch_over_strided and inframe_over_strided are the ratios of the medians."""
 import ctypes as C
 import argparse
 import json
@@ -132,15 +148,103 @@ def main_ptrs(args):
     return out
 
 
+BATCH_SHAPES = [
+    # (name, codec, len, lost, with result)
+    ("RS(255,251) len 10, 4 lost", lambda: ezrs.Codec.rs(255, 251), 10, [0, 3, 11, 13], True),
+    ("RS(255,223) len 223, 4 lost, no result", lambda: ezrs.Codec.rs(255, 223), 223, [5, 100, 222, 240], False),
+]
+SHARD_BYTES = [4 << 10, 64 << 10, 1 << 20]
+
+
+def main_batch(args):
+    L, sp = ezrs.lib(), ezrs._stream_ptr(None)
+    out = {"gib": args.gib, "reps": REPS, "device": torch.cuda.get_device_name(0), "results": []}
+    for name, mk, length, lost, use_result in BATCH_SHAPES:
+        for n in SHARD_BYTES:                       # 1-byte symbols
+            c = mk()
+            S, nlost = length + c.nroots, len(lost)
+            ns = max(1, -(-int(args.gib * (1 << 30)) // (S * n)))
+            frames = torch.empty((ns, S, n), dtype=torch.uint8, device="cuda")
+            g = torch.Generator(device="cuda").manual_seed(1)
+            step = max(1, (64 << 20) // (length * n))           # 64 Mi symbols at a time
+            for s0 in range(0, ns, step):
+                blk = frames[s0:s0 + step, :length]
+                blk.copy_(torch.randint(0, 256, blk.shape, generator=g, device="cuda", dtype=torch.uint8))
+            c.recon_plan(length, list(range(length, S))).reconstruct(frames)    # the parity
+            good = frames[:, lost].clone()
+            # the same shards, each a buffer of its own, placed by a random permutation of the slots
+            perm = torch.randperm(ns * S, generator=torch.Generator().manual_seed(2))
+            pool = torch.empty((ns * S, n), dtype=torch.uint8, device="cuda")
+            pool[perm.cuda()] = frames.view(ns * S, n)
+            slot = pool.unbind(0)
+            pl = perm.view(ns, S).tolist()
+            table, n_, align = ezrs.ptr_table([[slot[i] for i in row] for row in pl])
+            assert n_ == n and align == 16
+            host = table.cpu().numpy()
+            rows = [host.ctypes.data + 8 * S * s for s in range(ns)]    # one host pointer array per stripe
+            lost_slots = perm.view(ns, S)[:, lost].reshape(-1).cuda()
+            table_in = (frames.data_ptr() + torch.arange(ns * S, dtype=torch.int64).view(ns, S) * n).cuda()
+            plan = c.recon_plan(length, lost)
+            res, res_p = (torch.empty(ns * n, dtype=torch.int32, device="cuda") if use_result else None
+                          for _ in range(2))
+            rp = res_p.data_ptr() if use_result else 0
+
+            def loop():
+                for s in range(ns):
+                    L.ezrs_reconstruct_ptrs(plan._h, rows[s], n, rp + 4 * n * s if rp else None, sp)
+
+            fns = {"loop": loop,
+                   "batch": lambda: L.ezrs_reconstruct_ptrs_batch(plan._h, table.data_ptr(), S, n, ns, align,
+                                                                  rp or None, sp),
+                   "strided": lambda: plan.reconstruct(frames, result=res),
+                   "batch_inframe": lambda: L.ezrs_reconstruct_ptrs_batch(
+                       plan._h, table_in.data_ptr(), S, n, ns, 16, res.data_ptr() if use_result else None, sp)}
+            inframe = ("strided", "batch_inframe")
+            for what, fn in fns.items():            # each path once on garbage
+                frames[:, lost] = 0x5A
+                pool[lost_slots] = 0x5A
+                if use_result:
+                    res.fill_(77)
+                    res_p.fill_(77)
+                r = fn()
+                assert r is None or r is res or r == 0, (name, n, what)
+                torch.cuda.synchronize()
+                got = frames[:, lost] if what in inframe else pool[lost_slots].view(ns, nlost, n)
+                assert torch.equal(got, good), (name, n, what)
+                if use_result:
+                    assert bool(((res if what in inframe else res_p) == nlost).all()), (name, n, what)
+            fg = figure(fns)
+            torch.cuda.synchronize()
+            assert torch.equal(pool[lost_slots].view(ns, nlost, n), good), (name, n)
+            rec = {"shape": name, "len": length, "nroots": c.nroots, "nlost": nlost, "shard_bytes": n,
+                   "nstripes": ns, "total_bytes": ns * S * n, "result": use_result}
+            for k, v in fg.items():
+                rec[f"t_{k}_ms"], rec[f"spread_{k}"] = v["median_s"] * 1e3, v["spread"]
+            rec["batch_over_loop"] = fg["batch"]["median_s"] / fg["loop"]["median_s"]
+            rec["batch_over_strided"] = fg["batch"]["median_s"] / fg["strided"]["median_s"]
+            rec["inframe_over_strided"] = fg["batch_inframe"]["median_s"] / fg["strided"]["median_s"]
+            rec["loop_us_per_stripe"] = fg["loop"]["median_s"] / ns * 1e6
+            rec["iters"] = {k: v["iters"] for k, v in fg.items()}
+            out["results"].append(rec)
+            print(json.dumps(rec), flush=True)
+            del frames, good, pool, slot, table, table_in, res, res_p, plan, c, fns, lost_slots
+            torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gib", type=float, default=1.0)
     ap.add_argument("--ptrs", action="store_true", help="the pointer form against the strided form")
+    ap.add_argument("--batch", action="store_true", help="many small stripes: loop, batch call, strided call")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     args.out = args.out or os.path.join(ROOT, "profiles", "recon",
+                                        "recon_batch_bench.json" if args.batch else
                                         "recon_ptrs_bench.json" if args.ptrs else "recon_bench.json")
     torch.cuda.set_device(0)
+    if args.batch:
+        return write(args.out, main_batch(args))
     if args.ptrs:
         return write(args.out, main_ptrs(args))
     out = {"gib": args.gib, "reps": REPS, "device": torch.cuda.get_device_name(0), "results": []}

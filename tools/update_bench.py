@@ -6,6 +6,7 @@ comparison shares a kernel with the update.
 
     python tools/update_bench.py [--gib 1.0] [--out profiles/update/update_bench.json]
     python tools/update_bench.py --ptrs [--gib 1.0] [--out profiles/update/update_ptrs_bench.json]
+    python tools/update_bench.py --batch [--gib 1.0] [--out profiles/update/update_batch_bench.json]
 
 One frame per shape: len + nroots shards of `depth` symbols, symbol stride = depth, sized so that
 the frame holds at least --gib GiB (well past the 256 MiB Infinity Cache); newsyms is a packed
@@ -23,7 +24,23 @@ each an allocation of its own.  The calls alternate in the same process as above
 is called through the C ABI with its pointer arrays built once, as a C caller has them;
 ptrs_over_strided is the ratio of the medians.  A third figure, ptrs_inframe, is the pointer form on
 pointers to the rows of the strided frame and of its newsyms: the same addresses as the strided
-form, so that the kernels' addressing is compared apart from where the allocator put the shards."""
+form, so that the kernels' addressing is compared apart from where the allocator put the shards.
+
+--batch: many small stripes under one plan, three ways, alternating in the same process as above.
+Per shape and shard size (4 KiB, 64 KiB, 1 MiB) there are nstripes stripes, so many that all shards
+of the stripes together hold at least --gib GiB; on the device, for the pointer forms, are only the
+changed shards, the parity shards and the new symbols, each a buffer of its own in one pool, placed by
+a random permutation.
+  loop     one ezrs_update_ptrs call per stripe through the C ABI, the host pointer arrays built
+           once (the Python loop around the calls adds its own share to each of them)
+  batch    one ezrs_update_ptrs_batch call on the same shards, its tables built once by
+           ezrs.ptr_table
+  strided  one ezrs_update_interleaved call with nframes = nstripes on frame tensors of the same
+           bytes: the same arithmetic and no pointer fetch
+  batch_inframe  the batch call on tables of pointers to the rows of the strided frames and of
+           their newsyms: the same addresses as the strided call, so that the kernels' addressing
+           is compared apart from where the shards lie
+batch_over_loop, batch_over_strided and inframe_over_strided are the ratios of the medians."""
 import ctypes as C
 import argparse
 import json
@@ -134,15 +151,109 @@ def main_ptrs(args):
     return out
 
 
+BATCH_SHAPES = [
+    # (name, codec, len, changed)
+    ("RS(255,251) len 10, 1 changed", lambda: ezrs.Codec.rs(255, 251), 10, [3]),
+    ("RS(255,223) len 223, 1 changed", lambda: ezrs.Codec.rs(255, 223), 223, [100]),
+    ("RS(1023,1007) len 100, 1 changed", lambda: ezrs.Codec.rs(1023, 1007), 100, [50]),
+]
+SHARD_BYTES = [4 << 10, 64 << 10, 1 << 20]
+
+
+def main_batch(args):
+    L, sp = ezrs.lib(), ezrs._stream_ptr(None)
+    out = {"gib": args.gib, "reps": REPS, "device": torch.cuda.get_device_name(0), "results": []}
+    for name, mk, length, changed in BATCH_SHAPES:
+        for sb in SHARD_BYTES:
+            c = mk()
+            w, NR, nchg = c.info.datum_bytes, c.nroots, len(changed)
+            S, n = length + NR, sb // w
+            ns = max(1, -(-int(args.gib * (1 << 30)) // (S * sb)))
+            dt = torch.uint8 if w == 1 else torch.int16
+            g = torch.Generator(device="cuda").manual_seed(1)
+            frames = torch.empty((ns, S, n), dtype=dt, device="cuda")
+            step = max(1, (64 << 20) // (length * n))           # 64 Mi symbols at a time
+            for s0 in range(0, ns, step):
+                blk = frames[s0:s0 + step, :length]
+                blk.copy_(torch.randint(0, c.nn + 1, blk.shape, generator=g, device="cuda", dtype=torch.int32))
+            parity = list(range(length, S))
+            c.recon_plan(length, parity).reconstruct(frames)            # the first parity
+            newsyms = torch.randint(0, c.nn + 1, (ns, nchg, n), generator=g, device="cuda",
+                                    dtype=torch.int32).to(dt)
+            used = changed + parity
+            U = len(used) + nchg                    # buffers per stripe: changed | parity | new symbols
+            perm = torch.randperm(ns * U, generator=torch.Generator().manual_seed(2))
+            pool = torch.empty((ns * U, n), dtype=dt, device="cuda")
+            pool[perm.cuda()] = torch.cat([frames[:, used], newsyms], dim=1).reshape(ns * U, n)
+            orig, frames0 = pool.clone(), frames[:, used].clone()
+            slot = pool.unbind(0)
+            pl = perm.view(ns, U).tolist()
+            at = {p: i for i, p in enumerate(used)}
+            table, n_, a1 = ezrs.ptr_table([[slot[row[at[p]]] if p in at else None for p in range(S)]
+                                            for row in pl], optional=[p for p in range(S) if p not in at])
+            ntable, _, a2 = ezrs.ptr_table([[slot[i] for i in row[len(used):]] for row in pl])
+            align = min(a1, a2)
+            assert n_ == n and align == 16
+            host, nhost = table.cpu().numpy(), ntable.cpu().numpy()
+            rows = [(host.ctypes.data + 8 * S * s, nhost.ctypes.data + 8 * nchg * s) for s in range(ns)]
+            used_slots = perm.view(ns, U)[:, :len(used)].reshape(-1).cuda()
+            table_in = (frames.data_ptr() + torch.arange(ns * S, dtype=torch.int64).view(ns, S) * sb).cuda()
+            ntable_in = (newsyms.data_ptr() + torch.arange(ns * nchg, dtype=torch.int64).view(ns, nchg) * sb).cuda()
+            plan = c.update_plan(length, changed)
+
+            def loop():
+                for a, b in rows:
+                    L.ezrs_update_ptrs(plan._h, a, b, n, sp)
+
+            fns = {"loop": loop,
+                   "batch": lambda: L.ezrs_update_ptrs_batch(plan._h, table.data_ptr(), S, ntable.data_ptr(), nchg,
+                                                             n, ns, align, sp),
+                   "strided": lambda: plan.apply(frames, newsyms),
+                   "batch_inframe": lambda: L.ezrs_update_ptrs_batch(plan._h, table_in.data_ptr(), S,
+                                                                     ntable_in.data_ptr(), nchg, n, ns, 16, sp)}
+            inframe = ("strided", "batch_inframe")
+            want = None
+            for what, fn in fns.items():            # each path once, a nonzero delta, on the same input
+                pool.copy_(orig)
+                frames[:, used] = frames0
+                assert fn() in (0, None), (name, sb, what)
+                torch.cuda.synchronize()
+                got = frames[:, used].clone() if what in inframe else pool[used_slots].view(ns, len(used), n)
+                want = got.clone() if want is None else want
+                assert torch.equal(got, want) and not torch.equal(got, frames0), (name, sb, what)
+            fg = figure(fns)
+            torch.cuda.synchronize()
+            assert torch.equal(pool[used_slots].view(ns, len(used), n), want), (name, sb)
+            rec = {"shape": name, "len": length, "nroots": NR, "nchanged": nchg, "shard_bytes": sb,
+                   "nstripes": ns, "total_bytes": ns * S * sb, "update_bytes_moved": (3 * nchg + 2 * NR) * ns * sb}
+            for k, v in fg.items():
+                rec[f"t_{k}_ms"], rec[f"spread_{k}"] = v["median_s"] * 1e3, v["spread"]
+            rec["batch_over_loop"] = fg["batch"]["median_s"] / fg["loop"]["median_s"]
+            rec["batch_over_strided"] = fg["batch"]["median_s"] / fg["strided"]["median_s"]
+            rec["inframe_over_strided"] = fg["batch_inframe"]["median_s"] / fg["strided"]["median_s"]
+            rec["loop_us_per_stripe"] = fg["loop"]["median_s"] / ns * 1e6
+            rec["iters"] = {k: v["iters"] for k, v in fg.items()}
+            out["results"].append(rec)
+            print(json.dumps(rec), flush=True)
+            del frames, newsyms, pool, orig, frames0, slot, table, ntable, table_in, ntable_in, plan, c, fns
+            del used_slots, want
+            torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gib", type=float, default=1.0)
     ap.add_argument("--ptrs", action="store_true", help="the pointer form against the strided form")
+    ap.add_argument("--batch", action="store_true", help="many small stripes: loop, batch call, strided call")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     args.out = args.out or os.path.join(ROOT, "profiles", "update",
+                                        "update_batch_bench.json" if args.batch else
                                         "update_ptrs_bench.json" if args.ptrs else "update_bench.json")
     torch.cuda.set_device(0)
+    if args.batch:
+        return write(args.out, main_batch(args))
     if args.ptrs:
         return write(args.out, main_ptrs(args))
     out = {"gib": args.gib, "reps": REPS, "device": torch.cuda.get_device_name(0), "results": []}
