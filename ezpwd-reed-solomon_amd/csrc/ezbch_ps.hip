@@ -1,6 +1,6 @@
 // ezbch_ps.hip -- plane-sliced BCH remainders on MI355X (gfx950): the encode of BCH codecs whose
 // ECC is a whole number of bytes of at most 64 bits (C5: BCH(1023,983,4), 40 bits); the same tile
-// loop (ezbch_ps_tile.hpp) starts the fused decode in ezbch.hip.
+// loop (ezbch_ps_tile.hpp) starts the fused decode in ezbch_lane.hip.
 //
 // The remainder of a row: ECC = d(x) x^E mod g(x), data bits MSB first, ECC left-justified
 // big-endian (c++/ezpwd/bch:196-205; Djelic encode_bch).  The derivation is in
@@ -8,7 +8,7 @@
 // x^(8q + b), every bit plane of a row has the same weights w(q) = x^(8q) mod g, so a 32-bit word
 // holding one byte position of four rows is XORed whole into an E-word state; a three-level fold
 // inside each byte combines the planes (sum_b x^b U_b).  XOR networks only, no tables: the LFSR
-// kernel (k_bch_encode, ezbch.hip) spends a dependent 256-entry table read per data byte.
+// kernel (k_bch_encode, ezbch_lane.hip) spends a dependent 256-entry table read per data byte.
 //
 // A workgroup of kTW wavefronts per 256-row tile (four rows per lane, byte k of a word = row
 // 4l + k), two tile images per workgroup: the tile's rows arrive by 1 KiB LDS-DMA instructions as

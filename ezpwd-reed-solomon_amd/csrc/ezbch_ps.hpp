@@ -1,4 +1,4 @@
-// Plane-sliced BCH remainder kernels (ezbch_ps.hip), used by ezbch.hip.
+// Plane-sliced BCH remainder kernels (ezbch_ps.hip), used by ezbch.hip (codec id) and ezbch_lane.hip (launches).
 #pragma once
 #include <hip/hip_runtime.h>
 

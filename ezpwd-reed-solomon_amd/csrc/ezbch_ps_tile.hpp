@@ -1,6 +1,6 @@
 // ezbch_ps_tile.hpp -- the tile machinery of the plane-sliced BCH remainder kernels (see
 // ezbch_ps.hip): images, networks, fold and the persistent tile loop, shared by the encode kernel
-// (ezbch_ps.hip) and the fused decode kernel (ezbch.hip), which hand the loop what to do with each
+// (ezbch_ps.hip) and the fused decode kernel (ezbch_lane.hip), which hand the loop what to do with each
 // tile's remainders.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -168,3 +168,74 @@ def test_decode_inline(torch, codecs, m, t, L):
                 for k in np.nonzero(eres > 0)[0]:
                     np.testing.assert_array_equal(got[k, :eres[k]], eloc[k, :eres[k]],
                                                   err_msg=f"locations of row {k}: " + what)
+
+
+# ---- the lane kernels' staged-image write-back (k_bch_decode<T, NW> with lds_fix) ----------------
+# codecs without a plane-sliced path: (m, t) -> T, NW, where the field tables are, how locate is built
+LANE = {(12, 5): "T=5 NW=1, tables in LDS, locate inline",
+        (13, 8): "T=8 NW=2, tables in global memory, locate out of line"}
+LANE_LS = (1, 11, 59)
+LANE_NCW = (2, 63, 64, 65, 255, 256, 257, 513)      # a wave is 64 rows, a block 256
+LANE_CASES = [(m, t, L) for (m, t) in LANE for L in LANE_LS]
+
+
+@pytest.fixture(scope="module")
+def lane_codecs(torch):
+    import ezrs
+    return {mt: (O.BCH(*mt), ezrs.BCH(*mt)) for mt in LANE}
+
+
+def lane_flips(rows, L, oc, rng):
+    """Row k gets k mod (t + 2) flips, 0 .. t + 1; the first and the last row of every 64-row wave
+    get t.  All in the codeword's 8 L + ecc_bits bits, the first in the row's first byte and the
+    second in its last ECC byte that holds code bits, so both ends of a row's span are corrected."""
+    ncw, t, nbits = len(rows), oc.t, 8 * L + oc.ecc_bits
+    counts = np.arange(ncw) % (t + 2)
+    counts[0::64] = t
+    counts[63::64] = t
+    counts[ncw - 1] = t
+    for k in np.nonzero(counts)[0]:
+        pos = [int(rng.integers(0, 8)), int(rng.integers(nbits - 8, nbits))]
+        rest = [p for p in rng.permutation(nbits).tolist() if p not in pos]
+        for p in (pos + rest)[:counts[k]]:
+            rows[k, p >> 3] ^= 0x80 >> (p & 7)
+    return counts
+
+
+@pytest.mark.parametrize("m,t,L", LANE_CASES, ids=[f"m{m}t{t}-L{L}" for m, t, L in LANE_CASES])
+def test_lane_decode_packed_rows_at_odd_offset(torch, lane_codecs, m, t, L):
+    """Packed rows with inline ECC through the lane kernels, which correct in the block's staged
+    LDS image and write back the 16-byte pieces that hold flips: bases at byte offsets 0, 1 and 15,
+    batches around the wave (64 rows) and block (256 rows) sizes, 0 .. t + 1 flips per row.  Result,
+    error locations and the whole flat buffer (the bytes before the base and the tail included)
+    equal the oracle's.
+    The rows are staged, so that write-back runs, while rows_offset + 256 pitch + 8 <= 65536 bytes
+    of LDS, rows_offset = 2048 NW + the field tables when m <= 12 (((3 n + 1) 2 rounded up to 16):
+    BCH(12,5), pitch 59 + 8:  2048 + 24576 + 256 * 67 + 8 = 43784;
+    BCH(13,8), pitch 59 + 13: 4096 + 256 * 72 + 8 = 22536."""
+    oc, c = lane_codecs[m, t]
+    eb = oc.ecc_bytes
+    nw = (oc.ecc_bits + 63) // 64
+    tabs = ((3 * oc.n + 1) * 2 + 15) // 16 * 16 if m <= 12 else 0
+    assert 2048 * nw + tabs + 256 * (max(LANE_LS) + eb) + 8 <= 65536
+    rng = np.random.default_rng(4000 * m + L)
+    pitch = L + eb
+    for off in OFFSETS:
+        for ncw in LANE_NCW:
+            buf, rows = layout(rng, off, ncw, pitch)
+            oc.encode_batch(rows(buf), L)
+            counts = lane_flips(rows(buf), L, oc, rng)
+            exp = buf.copy()
+            eloc = np.zeros((ncw, t), np.uint32)
+            eres = oc.decode_batch(rows(exp), L, errloc=eloc)
+            assert (eres[counts <= t] == counts[counts <= t]).all()
+            flat, view = dev_rows(torch, buf, off, ncw, pitch, pitch)
+            loc = torch.zeros((ncw, t), dtype=torch.int32, device="cuda")
+            res = c.decode(view, L, errloc=loc).cpu().numpy()
+            what = f"off={off} ncw={ncw}"
+            np.testing.assert_array_equal(res, eres, err_msg="result: " + what)
+            np.testing.assert_array_equal(flat.cpu().numpy(), exp, err_msg="buffer: " + what)
+            got = loc.cpu().numpy().view(np.uint32)
+            for k in np.nonzero(eres > 0)[0]:
+                np.testing.assert_array_equal(got[k, :eres[k]], eloc[k, :eres[k]],
+                                              err_msg=f"locations of row {k}: " + what)
