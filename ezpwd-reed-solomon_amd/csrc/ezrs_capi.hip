@@ -616,24 +616,46 @@ int il_check(const ezrs_codec *c, const void *frames, size_t &frame_pitch, size_
     return 0;
 }
 
+// The frames of a pointer-form decode (ezrs_decode_ptrs / ezrs_decode_ptrs_batch): the table on the
+// device (pitch entries per stripe, every pointer a multiple of al), or else one stripe's pointers
+// by value, which the call first writes to the head of its workspace as a table of pitch entries.
+struct IlPtrs {
+    void *const *table;
+    size_t pitch, al;
+    const PtrTable *stripe;
+};
+
+// The head of a pointer-form decode's workspace: room for one stripe's table (ezrs_decode_ptrs).
+size_t il_ptrs_head(size_t positions) { return (positions * sizeof(void *) + 255) & ~(size_t)255; }
+
 // Both directions, pass by pass: gather, the codec's row kernels on the staged rows, scatter.
 //   encode (dec == null): gather the data symbols, scatter the parity symbols of every codeword
 //   decode: gather whole codewords, scatter whole rows of the codewords whose result is nonzero
+// pt != null: the frames are named by pointers (`frames` is null, depth the shard length).
 int il_run(const ezrs_codec *c, void *frames, size_t frame_pitch, size_t sym_stride, size_t depth,
-           unsigned len, size_t ncw, const DecodeOut *dec, const CallerWs *cw, void *stream) {
+           unsigned len, size_t ncw, const DecodeOut *dec, const CallerWs *cw, void *stream,
+           const IlPtrs *pt = nullptr) {
     DeviceGuard g(c->device);
     void *ws = nullptr;
-    if (int r = take_ws(c, cw, il_ws_bytes(c, len, ncw), stream, &ws)) return r;
-    hipStream_t st = static_cast<hipStream_t>(stream);
     const unsigned NR = c->dev.nroots;
     const size_t w = sym_bytes(c->dev), P = (size_t)len + NR;
+    const size_t head = pt ? il_ptrs_head(P) : 0;
+    if (int r = take_ws(c, cw, head + il_ws_bytes(c, len, ncw), stream, &ws)) return r;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    void *const *table = pt ? pt->table : nullptr;
+    if (pt && pt->stripe) {
+        hipError_t e = launch_il_table(*pt->stripe, (unsigned)P, static_cast<void **>(ws), st);
+        if (e != hipSuccess) return hip_fail(e, "pointer table launch");
+        table = static_cast<void *const *>(ws);
+    }
+    ws = static_cast<char *>(ws) + head;
     const size_t chunk = il_chunk_rows(c, len, ncw);
     char *stage =static_cast<char *>(ws) + il_ws_codec(c, chunk);
     for (size_t k0 = 0; k0 < ncw; k0 += chunk) {
         const size_t n = ncw - k0 < chunk ? ncw - k0 : chunk;
-        IlArgs a{frames, frame_pitch, sym_stride, depth, stage, P, k0, (uint32_t)n, 0, dec ? len + NR : len,
-                 nullptr};
-        hipError_t e = launch_il_gather(c->dev, a, st);
+        IlPtrArgs a{{frames, frame_pitch, sym_stride, depth, stage, P, k0, (uint32_t)n, 0, dec ? len + NR : len,
+                     nullptr}, table, pt ? pt->pitch : 0};
+        hipError_t e = pt ? launch_il_gather(c->dev, a, pt->al, st) : launch_il_gather(c->dev, (const IlArgs &)a, st);
         if (e != hipSuccess) return hip_fail(e, "interleaved gather launch");
         if (!dec) {
             if (int r = run_encode(c, EncodeArgs{stage, P, len, stage + (size_t)len * w, P, n}, ws, stream))
@@ -645,7 +667,8 @@ int il_run(const ezrs_codec *c, void *frames, size_t frame_pitch, size_t sym_str
                 return r;
             a.result = dec->result + k0;
         }
-        if ((e = launch_il_scatter(c->dev, a, st)) != hipSuccess) return hip_fail(e, "interleaved scatter launch");
+        e = pt ? launch_il_scatter(c->dev, a, pt->al, st) : launch_il_scatter(c->dev, (const IlArgs &)a, st);
+        if (e != hipSuccess) return hip_fail(e, "interleaved scatter launch");
     }
     return 0;
 }
@@ -990,6 +1013,93 @@ int ezrs_update_ptrs_batch(const ezrs_update *p, void *const *table, size_t tabl
     hipError_t e = launch_update(a, nstripes, align, t, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return hip_fail(e, "update launch");
     return 0;
+}
+
+// ---- pointer forms of the staged decode: errors and erasures in stripes of separate buffers --------
+namespace {
+
+// ezrs_decode_ptrs(_ws): one stripe, the pointers by value; cw == null uses the stream's workspace.
+int decode_ptrs(const ezrs_codec *c, void *const *shards, unsigned len, size_t shard_len, const DecodeOut &o,
+                const CallerWs *cw, void *stream) {
+    if (!c || !shards || !o.result) return -EINVAL;
+    if (len < 1 || len > c->dev.load) return -EINVAL;
+    const size_t w = sym_bytes(c->dev), P = (size_t)len + c->dev.nroots;
+    if (P > kPtrsMax) {
+        g_last_error = "decode_ptrs: len + NROOTS above EZRS_PTRS_MAX pointers";
+        return -ENOTSUP;
+    }
+    if (shard_len == 0) return 0;
+    if (shard_len > SIZE_MAX / w) return -EINVAL;
+    PtrTable tab{};
+    PtrRanges rg;
+    for (size_t p = 0; p < P; ++p) {                // every buffer is read and may be written
+        if (!(tab.p[p] = shards[p])) return ptrs_fail("decode_ptrs: a shard is NULL");
+        rg.add(shards[p], shard_len * w);
+    }
+    rg.nwritten = rg.n;
+    if (rg.clash()) return ptrs_fail("decode_ptrs: two shards' buffers overlap");
+    if (int r = check_decode_out(c, shard_len, o)) return r;
+    const IlPtrs pt{nullptr, P, rg.al, &tab};
+    return il_run(c, nullptr, 0, 0, shard_len, len, shard_len, &o, cw, stream, &pt);
+}
+
+// ezrs_decode_ptrs_batch(_ws): the table on the device.
+int decode_ptrs_batch(const ezrs_codec *c, void *const *table, size_t table_pitch, unsigned len,
+                      size_t shard_len, size_t nstripes, unsigned align, const DecodeOut &o,
+                      const CallerWs *cw, void *stream) {
+    if (!c || !table || !o.result) return -EINVAL;
+    if (len < 1 || len > c->dev.load) return -EINVAL;
+    if (int r = batch_check("decode_ptrs_batch", table_pitch, (size_t)len + c->dev.nroots, shard_len, nstripes,
+                            align, sym_bytes(c->dev)))
+        return r < 0 ? r : 0;
+    const size_t ncw = nstripes * shard_len;
+    if (int r = check_decode_out(c, ncw, o)) return r;
+    const IlPtrs pt{table, table_pitch, align, nullptr};
+    return il_run(c, nullptr, 0, 0, shard_len, len, ncw, &o, cw, stream, &pt);
+}
+
+} // namespace
+
+size_t ezrs_decode_ptrs_workspace_bytes(const ezrs_codec *c, unsigned len, size_t shard_len, size_t nstripes) {
+    if (!c || len < 1 || len > c->dev.load || shard_len == 0 || nstripes == 0 || shard_len > SIZE_MAX / nstripes)
+        return 0;
+    return il_ptrs_head((size_t)len + c->dev.nroots) + il_ws_bytes(c, len, shard_len * nstripes);
+}
+
+int ezrs_decode_ptrs(const ezrs_codec *c, void *const *shards, unsigned len, size_t shard_len,
+                     const uint32_t *eras, size_t eras_stride, const uint32_t *neras, int32_t *result,
+                     uint32_t *positions, size_t pos_stride, void *corr, size_t corr_stride, void *stream) {
+    return decode_ptrs(c, shards, len, shard_len,
+                       {eras, eras_stride, neras, result, positions, pos_stride, corr, corr_stride}, nullptr, stream);
+}
+
+int ezrs_decode_ptrs_ws(const ezrs_codec *c, void *const *shards, unsigned len, size_t shard_len,
+                        const uint32_t *eras, size_t eras_stride, const uint32_t *neras, int32_t *result,
+                        uint32_t *positions, size_t pos_stride, void *corr, size_t corr_stride, void *ws,
+                        size_t ws_bytes, void *stream) {
+    const CallerWs cw{ws, ws_bytes};
+    return decode_ptrs(c, shards, len, shard_len,
+                       {eras, eras_stride, neras, result, positions, pos_stride, corr, corr_stride}, &cw, stream);
+}
+
+int ezrs_decode_ptrs_batch(const ezrs_codec *c, void *const *table, size_t table_pitch, unsigned len,
+                           size_t shard_len, size_t nstripes, unsigned align, const uint32_t *eras,
+                           size_t eras_stride, const uint32_t *neras, int32_t *result, uint32_t *positions,
+                           size_t pos_stride, void *corr, size_t corr_stride, void *stream) {
+    return decode_ptrs_batch(c, table, table_pitch, len, shard_len, nstripes, align,
+                             {eras, eras_stride, neras, result, positions, pos_stride, corr, corr_stride}, nullptr,
+                             stream);
+}
+
+int ezrs_decode_ptrs_batch_ws(const ezrs_codec *c, void *const *table, size_t table_pitch, unsigned len,
+                              size_t shard_len, size_t nstripes, unsigned align, const uint32_t *eras,
+                              size_t eras_stride, const uint32_t *neras, int32_t *result, uint32_t *positions,
+                              size_t pos_stride, void *corr, size_t corr_stride, void *ws, size_t ws_bytes,
+                              void *stream) {
+    const CallerWs cw{ws, ws_bytes};
+    return decode_ptrs_batch(c, table, table_pitch, len, shard_len, nstripes, align,
+                             {eras, eras_stride, neras, result, positions, pos_stride, corr, corr_stride}, &cw,
+                             stream);
 }
 
 int ezrs_update_bitmatrix(unsigned symbol_bits, unsigned poly, unsigned fcr, unsigned prim, unsigned nroots,

@@ -28,6 +28,17 @@
 // most 2-way (free on ds_write_b32) for LS = 8 and 16; the row side's 4 rows x 8 slots per
 // 32-lane group are distinct up to each row's alignment shift (at most 2-way).
 // The only division is one per thread and tile (k -> frame, column), 32-bit when it fits.
+//
+// Addressing policy, chosen by the argument struct A of both kernels.  Strided (IlArgs): symbol s of
+// codeword (f, j) is element f * frame_pitch + s * sym_stride + j of `frames`.  Pointers
+// (IlPtrArgs; ezrs_decode_ptrs / ezrs_decode_ptrs_batch): it is element j of the buffer
+// table[f * pitch + s], the table in device memory.  Only the frame side differs: lanes along s
+// read consecutive table entries, lanes along j of one stripe the same entry.  A tile that lies in
+// one stripe (every tile once shard_len >= 256 + 255) holds the pointers of the current symbol
+// chunk in LDS (at most 128 entries, one coalesced table read per chunk), so the symbol accesses
+// do not wait for a table load each; a tile that spans stripes reads its entries from the table,
+// one per symbol access.  The pointer fast path needs shard_len and every pointer to be multiples
+// of 4; tiles start at multiples of 256 codewords, so a quad of codewords never straddles stripes.
 #include "ezrs_internal.hpp"
 
 namespace ezrs {
@@ -50,62 +61,146 @@ __device__ __forceinline__ void transpose4x4(const uint32_t (&a)[4], uint32_t (&
     out[3] = __builtin_amdgcn_perm(u23, u01, 0x07060302u);
 }
 
-// Element offset of codeword k's symbol 0 in the frames.
-__device__ __forceinline__ size_t frame_off(const IlArgs &a, size_t k) {
-    size_t f, j;
-    if (((k | a.depth) >> 32) == 0) {               // 32-bit division (see shard_row)
-        const uint32_t k32 = (uint32_t)k, d32 = (uint32_t)a.depth, f32 = k32 / d32;
+// Codeword k = f * depth + j.
+__device__ __forceinline__ void frame_of(size_t depth, size_t k, size_t &f, size_t &j) {
+    if (((k | depth) >> 32) == 0) {                 // 32-bit division (see shard_row)
+        const uint32_t k32 = (uint32_t)k, d32 = (uint32_t)depth, f32 = k32 / d32;
         f = f32;
         j = k32 - f32 * d32;
     } else {
-        f = k / a.depth;
-        j = k - f * a.depth;
+        f = k / depth;
+        j = k - f * depth;
     }
+}
+
+// Element offset of codeword k's symbol 0 in the frames.
+__device__ __forceinline__ size_t frame_off(const IlArgs &a, size_t k) {
+    size_t f, j;
+    frame_of(a.depth, k, f, j);
     return f * a.frame_pitch + j;
 }
 
+template <class A>
+constexpr bool kPtrs = std::is_same_v<A, IlPtrArgs>;
+
+// What a tile of the pointer policy keeps in LDS besides off[] (which holds j): the first table
+// entry of every codeword's stripe and, for a tile in one stripe, the buffers of the symbol chunk.
+template <bool PTRS>
+struct PtrTile {};
+template <>
+struct PtrTile<true> {
+    size_t row[kTile];
+    void *sym[kChunkB];
+};
+
+// Pointer policy: (stripe, element) of the tile's codewords k .. k + nk - 1 into off[] and row[].
+// one: the tile lies in one stripe, whose first table entry is row0 (both uniform over the tile).
+// One division per tile (uniform) where the tile lies in one stripe, else one per thread.
+__device__ __forceinline__ void ptr_tile(const IlPtrArgs &a, size_t k, unsigned nk, unsigned t, size_t *off,
+                                         PtrTile<true> &pt, bool &one, size_t &row0) {
+    size_t f, j;
+    frame_of(a.depth, k, f, j);
+    one = j + nk <= a.depth;
+    row0 = f * a.pitch;
+    if (one) j += t;
+    else frame_of(a.depth, k + t, f, j);            // t >= nk: an entry that is never used
+    off[t] = j;
+    pt.row[t] = f * a.pitch;
+}
+
+// Entry e of the pointer table, read as the global memory it is (see At).
+__device__ __forceinline__ void *table_at(const IlPtrArgs &a, size_t e) {
+    typedef void *Ptr;
+    return ((__attribute__((address_space(1))) const Ptr *)a.table)[e];
+}
+
+// The frame side of one symbol chunk (first symbol sa) under either policy.  cw(off[kk]): what is
+// fixed for codeword kk of the tile, the address of its symbol sa (strided) or its element j
+// (pointers); sym(that, kk, s): where its symbol sa + s is; as<U>: that address as a U.  The
+// buffers of the pointer policy are global memory and typed so: a generic pointer would make every
+// symbol access a flat one, which counts on the LDS counter too, so the wait for the next pointer
+// out of LDS would wait for all the symbol loads before it.  ONE (pointers): the tile lies in one
+// stripe and the chunk's pointers are in LDS; a template parameter, so that the choice is made once
+// per chunk and not in a branch around every access, which would keep a lane's pointer reads apart.
+template <typename T, class A, bool ONE>
+struct At {
+    static constexpr bool PTRS = kPtrs<A>;
+    template <typename U>
+    using Mem = std::conditional_t<PTRS, __attribute__((address_space(1))) U *, U *>;
+    typedef std::conditional_t<PTRS, size_t, T *> Cw;
+    typedef Mem<T> Sym;
+    const A &a;
+    T *frames;
+    const PtrTile<PTRS> &pt;
+    unsigned sa;
+    __device__ __forceinline__ Cw cw(size_t off) const {
+        if constexpr (PTRS) return off;
+        else return frames + off + (size_t)sa * a.sym_stride;
+    }
+    __device__ __forceinline__ Sym sym(Cw p, unsigned kk, unsigned s) const {
+        if constexpr (PTRS) return (Sym)static_cast<T *>(ONE ? pt.sym[s] : table_at(a, pt.row[kk] + sa + s)) + p;
+        else return p + (size_t)s * a.sym_stride;
+    }
+    template <typename U>
+    static __device__ __forceinline__ Mem<U> as(Sym q) {
+        if constexpr (PTRS) return (Mem<U>)q;
+        else return reinterpret_cast<U *>(q);
+    }
+};
+
 // Frames -> rows.  lg = log2(LS).
-template <typename T, bool FAST>
-__global__ void __launch_bounds__(256) k_il_gather(IlArgs a, unsigned lg) {
+template <typename T, bool FAST, class A>
+__global__ void __launch_bounds__(256) k_il_gather(A a, unsigned lg) {
+    constexpr bool PTRS = kPtrs<A>;
     // 16 guard bytes on either side: a partial slot's aligned dword reads may start before row 0
     // and end after row 255 (those bytes are never stored)
     __shared__ __attribute__((aligned(16))) uint8_t lds[16 + kTile * kPitchB + 16];
     __shared__ size_t off[kTile];
+    __shared__ PtrTile<PTRS> pt;
     uint8_t *const tile = lds + 16;
     constexpr unsigned SC = kChunkB / sizeof(T), PT = kPitchB / sizeof(T);
     const unsigned t = threadIdx.x;
     const size_t kt0 = (size_t)blockIdx.x * kTile;
     const unsigned nk = a.n - kt0 < kTile ? (unsigned)(a.n - kt0) : kTile;
-    off[t] = t < nk ? frame_off(a, a.k0 + kt0 + t) : 0;
+    bool one = false;
+    size_t row0 = 0;
+    if constexpr (PTRS) ptr_tile(a, a.k0 + kt0, nk, t, off, pt, one, row0);
+    else off[t] = t < nk ? frame_off(a, a.k0 + kt0 + t) : 0;
     const T *frames = static_cast<const T *>(a.frames);
     uint8_t *rb = static_cast<uint8_t *>(a.rows);
     const unsigned ls = 1u << lg, si = t & (ls - 1), ki = t >> lg, kstep = 256u >> lg;
     for (unsigned sa = a.s0; sa < a.s1; sa += SC) {
         const unsigned ns = a.s1 - sa < SC ? a.s1 - sa : SC;
+        if constexpr (PTRS)                         // the last chunk's frame side is behind a barrier
+            if (one && t < ns) pt.sym[t] = table_at(a, row0 + sa + t);
         __syncthreads();                            // off[] written; the tile's last chunk stored
-        if constexpr (FAST) {
+        const auto frame_side = [&](auto at) {
+            if constexpr (FAST) {
 #pragma unroll 4
-            for (unsigned q = ki; 4 * q < nk; q += kstep) {
-                const uint8_t *p = reinterpret_cast<const uint8_t *>(frames) + off[4 * q] + (size_t)sa * a.sym_stride;
-                for (unsigned s4 = 4 * si; s4 < ns; s4 += 4 * ls) {
-                    uint32_t in[4], out[4];
+                for (unsigned q = ki; 4 * q < nk; q += kstep) {
+                    const auto p = at.cw(off[4 * q]);
+                    for (unsigned s4 = 4 * si; s4 < ns; s4 += 4 * ls) {
+                        uint32_t in[4], out[4];
 #pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        in[i] = s4 + i < ns ? *reinterpret_cast<const uint32_t *>(p + (size_t)(s4 + i) * a.sym_stride) : 0u;
-                    transpose4x4(in, out);          // out[i]: symbols s4..s4+3 of codeword 4q + i
+                        for (int i = 0; i < 4; ++i)
+                            in[i] = s4 + i < ns ? *at.template as<const uint32_t>(at.sym(p, 4 * q, s4 + i)) : 0u;
+                        transpose4x4(in, out);          // out[i]: symbols s4..s4+3 of codeword 4q + i
 #pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        *reinterpret_cast<uint32_t *>(tile + (4 * q + i) * kPitchB + s4) = out[i];
+                        for (int i = 0; i < 4; ++i)
+                            *reinterpret_cast<uint32_t *>(tile + (4 * q + i) * kPitchB + s4) = out[i];
+                    }
+                }
+            } else {
+                T *lt = reinterpret_cast<T *>(tile);
+                for (unsigned kk = ki; kk < nk; kk += kstep) {
+                    const auto p = at.cw(off[kk]);
+#pragma unroll 8
+                    for (unsigned s = si; s < ns; s += ls) lt[kk * PT + s] = *at.sym(p, kk, s);
                 }
             }
-        } else {
-            T *lt = reinterpret_cast<T *>(tile);
-            for (unsigned kk = ki; kk < nk; kk += kstep) {
-                const T *p = frames + off[kk] + (size_t)sa * a.sym_stride;
-#pragma unroll 8
-                for (unsigned s = si; s < ns; s += ls) lt[kk * PT + s] = p[(size_t)s * a.sym_stride];
-            }
-        }
+        };
+        if (PTRS && one) frame_side(At<const T, A, PTRS>{a, frames, pt, sa});
+        else frame_side(At<const T, A, false>{a, frames, pt, sa});
         __syncthreads();
         // rows: the 16-byte aligned slots of every row's segment [g, g + nb)
         const unsigned nb = ns * (unsigned)sizeof(T);
@@ -142,10 +237,12 @@ __global__ void __launch_bounds__(256) k_il_gather(IlArgs a, unsigned lg) {
 }
 
 // Rows -> frames, for every codeword of the tile (result == null) or those with a nonzero result.
-template <typename T, bool FAST>
-__global__ void __launch_bounds__(256) k_il_scatter(IlArgs a, unsigned lg) {
+template <typename T, bool FAST, class A>
+__global__ void __launch_bounds__(256) k_il_scatter(A a, unsigned lg) {
+    constexpr bool PTRS = kPtrs<A>;
     __shared__ __attribute__((aligned(16))) uint8_t tile[kTile * kPitchB];
     __shared__ size_t off[kTile];
+    __shared__ PtrTile<PTRS> pt;
     __shared__ __attribute__((aligned(4))) uint8_t flag[kTile];   // 1: write this codeword back
     constexpr unsigned SC = kChunkB / sizeof(T), PT = kPitchB / sizeof(T);
     const unsigned t = threadIdx.x;
@@ -154,7 +251,10 @@ __global__ void __launch_bounds__(256) k_il_scatter(IlArgs a, unsigned lg) {
     const bool mine = t < nk && (!a.result || a.result[kt0 + t] != 0);
     flag[t] = mine;
     if (!__syncthreads_or(mine)) return;            // a tile of clean codewords: nothing to write
-    off[t] = mine ? frame_off(a, a.k0 + kt0 + t) : 0;
+    bool one = false;
+    size_t row0 = 0;
+    if constexpr (PTRS) ptr_tile(a, a.k0 + kt0, nk, t, off, pt, one, row0);
+    else off[t] = mine ? frame_off(a, a.k0 + kt0 + t) : 0;
     T *frames = static_cast<T *>(a.frames);
     const uint8_t *rb = static_cast<const uint8_t *>(a.rows);
     const unsigned ls = 1u << lg, si = t & (ls - 1), ki = t >> lg, kstep = 256u >> lg;
@@ -162,6 +262,8 @@ __global__ void __launch_bounds__(256) k_il_scatter(IlArgs a, unsigned lg) {
         const unsigned ns = a.s1 - sa < SC ? a.s1 - sa : SC;
         const unsigned nb = ns * (unsigned)sizeof(T);
         __syncthreads();
+        if constexpr (PTRS)                         // read after the next barrier
+            if (one && t < ns) pt.sym[t] = table_at(a, row0 + sa + t);
         // rows -> LDS: 16-byte LDS slots from aligned global dwords (reads may run up to 19 bytes
         // past the segment: inside the staging area, il_stage_bytes)
         for (unsigned e = t; e < nk * (kChunkB / 16); e += 256) {
@@ -178,42 +280,46 @@ __global__ void __launch_bounds__(256) k_il_scatter(IlArgs a, unsigned lg) {
             lw[3] = __builtin_amdgcn_alignbyte(w4, w3, r);
         }
         __syncthreads();
-        if constexpr (FAST) {
-            for (unsigned q = ki; 4 * q < nk; q += kstep) {
-                const uint32_t fl = *reinterpret_cast<const uint32_t *>(flag + 4 * q);
-                if (!fl) continue;
-                // off[] of the quad's first flagged codeword gives the quad's base
-                const unsigned i0 = (fl & 0xFFu) ? 0 : (fl & 0xFF00u) ? 1 : (fl & 0xFF0000u) ? 2 : 3;
-                uint8_t *p = reinterpret_cast<uint8_t *>(frames) + (off[4 * q + i0] - i0) + (size_t)sa * a.sym_stride;
-                for (unsigned s4 = 4 * si; s4 < ns; s4 += 4 * ls) {
-                    uint32_t in[4], out[4];
+        const auto frame_side = [&](auto at) {
+            if constexpr (FAST) {
+                for (unsigned q = ki; 4 * q < nk; q += kstep) {
+                    const uint32_t fl = *reinterpret_cast<const uint32_t *>(flag + 4 * q);
+                    if (!fl) continue;
+                    // off[] of the quad's first flagged codeword gives the quad's base
+                    const unsigned i0 = (fl & 0xFFu) ? 0 : (fl & 0xFF00u) ? 1 : (fl & 0xFF0000u) ? 2 : 3;
+                    const auto p = at.cw(off[4 * q + i0] - i0);
+                    for (unsigned s4 = 4 * si; s4 < ns; s4 += 4 * ls) {
+                        uint32_t in[4], out[4];
 #pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        in[i] = *reinterpret_cast<const uint32_t *>(tile + (4 * q + i) * kPitchB + s4);
-                    transpose4x4(in, out);          // out[m]: symbol s4 + m of codewords 4q..4q+3
+                        for (int i = 0; i < 4; ++i)
+                            in[i] = *reinterpret_cast<const uint32_t *>(tile + (4 * q + i) * kPitchB + s4);
+                        transpose4x4(in, out);          // out[m]: symbol s4 + m of codewords 4q..4q+3
 #pragma unroll
-                    for (int m = 0; m < 4; ++m) {
-                        if (s4 + m >= ns) continue;
-                        uint8_t *dst = p + (size_t)(s4 + m) * a.sym_stride;
-                        if (fl == 0x01010101u) {
-                            *reinterpret_cast<uint32_t *>(dst) = out[m];
-                        } else {
+                        for (int m = 0; m < 4; ++m) {
+                            if (s4 + m >= ns) continue;
+                            const auto dst = at.sym(p, 4 * q, s4 + m);
+                            if (fl == 0x01010101u) {
+                                *at.template as<uint32_t>(dst) = out[m];
+                            } else {
 #pragma unroll
-                            for (int b = 0; b < 4; ++b)
-                                if ((fl >> (8 * b)) & 0xFFu) dst[b] = (uint8_t)(out[m] >> (8 * b));
+                                for (int b = 0; b < 4; ++b)
+                                    if ((fl >> (8 * b)) & 0xFFu) dst[b] = (uint8_t)(out[m] >> (8 * b));
+                            }
                         }
                     }
                 }
-            }
-        } else {
-            const T *lt = reinterpret_cast<const T *>(tile);
-            for (unsigned kk = ki; kk < nk; kk += kstep) {
-                if (!flag[kk]) continue;
-                T *p = frames + off[kk] + (size_t)sa * a.sym_stride;
+            } else {
+                const T *lt = reinterpret_cast<const T *>(tile);
+                for (unsigned kk = ki; kk < nk; kk += kstep) {
+                    if (!flag[kk]) continue;
+                    const auto p = at.cw(off[kk]);
 #pragma unroll 4
-                for (unsigned s = si; s < ns; s += ls) p[(size_t)s * a.sym_stride] = lt[kk * PT + s];
+                    for (unsigned s = si; s < ns; s += ls) *at.sym(p, kk, s) = lt[kk * PT + s];
+                }
             }
-        }
+        };
+        if (PTRS && one) frame_side(At<T, A, PTRS>{a, frames, pt, sa});
+        else frame_side(At<T, A, false>{a, frames, pt, sa});
     }
 }
 
@@ -237,29 +343,56 @@ static unsigned lanes_log2(size_t depth, bool fast) {
     return lg;
 }
 
-template <bool GATHER>
-static hipError_t launch(const DevCodec &d, const IlArgs &a, hipStream_t s) {
+template <bool GATHER, class A>
+static hipError_t launch(const DevCodec &d, const A &a, bool fast, hipStream_t s) {
     if (!a.n || a.s0 >= a.s1) return hipSuccess;
     if (a.n > kIlMaxRows) return hipErrorInvalidValue;
-    const bool fast = fast_ok(d, a);
     const unsigned lg = lanes_log2(a.depth, fast);
     const dim3 grid((unsigned)((a.n + kTile - 1) / kTile)), block(256);
     if (d.mm > 8) {
-        if (GATHER) hipLaunchKernelGGL((k_il_gather<uint16_t, false>), grid, block, 0, s, a, lg);
-        else hipLaunchKernelGGL((k_il_scatter<uint16_t, false>), grid, block, 0, s, a, lg);
+        if (GATHER) hipLaunchKernelGGL((k_il_gather<uint16_t, false, A>), grid, block, 0, s, a, lg);
+        else hipLaunchKernelGGL((k_il_scatter<uint16_t, false, A>), grid, block, 0, s, a, lg);
     } else if (fast) {
-        if (GATHER) hipLaunchKernelGGL((k_il_gather<uint8_t, true>), grid, block, 0, s, a, lg);
-        else hipLaunchKernelGGL((k_il_scatter<uint8_t, true>), grid, block, 0, s, a, lg);
+        if (GATHER) hipLaunchKernelGGL((k_il_gather<uint8_t, true, A>), grid, block, 0, s, a, lg);
+        else hipLaunchKernelGGL((k_il_scatter<uint8_t, true, A>), grid, block, 0, s, a, lg);
     } else {
-        if (GATHER) hipLaunchKernelGGL((k_il_gather<uint8_t, false>), grid, block, 0, s, a, lg);
-        else hipLaunchKernelGGL((k_il_scatter<uint8_t, false>), grid, block, 0, s, a, lg);
+        if (GATHER) hipLaunchKernelGGL((k_il_gather<uint8_t, false, A>), grid, block, 0, s, a, lg);
+        else hipLaunchKernelGGL((k_il_scatter<uint8_t, false, A>), grid, block, 0, s, a, lg);
     }
     return hipGetLastError();
 }
 
+// Pointer fast path: uint8_t, the shard length and every pointer multiples of 4.
+static bool fast_ok(const DevCodec &d, const IlPtrArgs &a, size_t al) { return d.mm <= 8 && ((a.depth | al) & 3) == 0; }
+
+// One stripe's pointers from the kernel arguments into device memory, one entry per thread.  The
+// entry is read where the kernel arguments lie (`tab` is the first of them), as k_recon's table
+// policy does: indexed as tab.p[threadIdx.x], a lane-varying index, the compiler would copy the
+// whole table to scratch first.
+__global__ void __launch_bounds__(kPtrsMax) k_il_table(PtrTable tab, unsigned n, void **out) {
+    typedef void *Ptr;                              // a generic pointer that lies in the kernarg segment
+    typedef __attribute__((address_space(4))) const Ptr Ent;
+    Ent *const args = (Ent *)__builtin_amdgcn_kernarg_segment_ptr();
+    if (threadIdx.x < n) out[threadIdx.x] = args[threadIdx.x];
+}
+
 } // namespace il
 
-hipError_t launch_il_gather(const DevCodec &d, const IlArgs &a, hipStream_t s) { return il::launch<true>(d, a, s); }
-hipError_t launch_il_scatter(const DevCodec &d, const IlArgs &a, hipStream_t s) { return il::launch<false>(d, a, s); }
+hipError_t launch_il_gather(const DevCodec &d, const IlArgs &a, hipStream_t s) {
+    return il::launch<true>(d, a, il::fast_ok(d, a), s);
+}
+hipError_t launch_il_scatter(const DevCodec &d, const IlArgs &a, hipStream_t s) {
+    return il::launch<false>(d, a, il::fast_ok(d, a), s);
+}
+hipError_t launch_il_gather(const DevCodec &d, const IlPtrArgs &a, size_t al, hipStream_t s) {
+    return il::launch<true>(d, a, il::fast_ok(d, a, al), s);
+}
+hipError_t launch_il_scatter(const DevCodec &d, const IlPtrArgs &a, size_t al, hipStream_t s) {
+    return il::launch<false>(d, a, il::fast_ok(d, a, al), s);
+}
+hipError_t launch_il_table(const PtrTable &tab, unsigned n, void **out, hipStream_t s) {
+    hipLaunchKernelGGL(il::k_il_table, dim3(1), dim3(kPtrsMax), 0, s, tab, n, out);
+    return hipGetLastError();
+}
 
 } // namespace ezrs

@@ -194,6 +194,18 @@ inline size_t il_stage_bytes(size_t n, size_t row_pitch, size_t w) {
 }
 hipError_t launch_il_gather(const DevCodec &d, const IlArgs &a, hipStream_t s);
 hipError_t launch_il_scatter(const DevCodec &d, const IlArgs &a, hipStream_t s);
+// The pointer policy of the same two kernels (ezrs_decode_ptrs / ezrs_decode_ptrs_batch): frames
+// (stripes) whose symbol rows are buffers of their own, named by a pointer table in DEVICE memory
+// that the kernels read while they run.  Symbol s of codeword k = f * depth + j is element j of the
+// buffer table[f * pitch + s]; frames is null, frame_pitch and sym_stride are 0, depth is the shard
+// length.  al: what every pointer of the table is a multiple of (the caller's promise, or the OR of
+// the addresses).
+struct IlPtrArgs : IlArgs {
+    void *const *table;
+    size_t pitch;
+};
+hipError_t launch_il_gather(const DevCodec &d, const IlPtrArgs &a, size_t al, hipStream_t s);
+hipError_t launch_il_scatter(const DevCodec &d, const IlPtrArgs &a, size_t al, hipStream_t s);
 
 // Shared-erasure reconstruction of interleaved frames (ezrs_recon.hip; ezrs_recon_create /
 // ezrs_reconstruct_interleaved): one constant GF matrix per loss pattern, applied to the survivors
@@ -269,6 +281,9 @@ constexpr unsigned kPtrsMax = EZRS_PTRS_MAX;
 struct PtrTable {
     void *p[kPtrsMax];
 };
+// ezrs_decode_ptrs: the n pointers of one stripe, by position, written to out[0 .. n-1] in device
+// memory (the head of the call's workspace), so that the call runs the table policy of IlPtrArgs.
+hipError_t launch_il_table(const PtrTable &tab, unsigned n, void **out, hipStream_t s);
 struct ReconPtrArgs : ReconArgs {
     PtrTable tab;
 };

@@ -112,6 +112,15 @@ def lib():
         L.ezrs_update_ptrs.argtypes = [_vp, _vp, _vp, _sz, _vp]
         L.ezrs_reconstruct_ptrs_batch.argtypes = [_vp, _vp, _sz, _sz, _sz, _u, _vp, _vp]
         L.ezrs_update_ptrs_batch.argtypes = [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _u, _vp]
+        L.ezrs_decode_ptrs_workspace_bytes.restype = _sz
+        L.ezrs_decode_ptrs_workspace_bytes.argtypes = [_vp, _u, _sz, _sz]
+        L.ezrs_decode_ptrs.argtypes = [_vp, _vp, _u, _sz, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _sz, _vp]
+        L.ezrs_decode_ptrs_ws.argtypes = [_vp, _vp, _u, _sz, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _sz,
+                                          _vp, _sz, _vp]
+        L.ezrs_decode_ptrs_batch.argtypes = [_vp, _vp, _sz, _u, _sz, _sz, _u, _vp, _sz, _vp, _vp, _vp,
+                                             _sz, _vp, _sz, _vp]
+        L.ezrs_decode_ptrs_batch_ws.argtypes = [_vp, _vp, _sz, _u, _sz, _sz, _u, _vp, _sz, _vp, _vp,
+                                                _vp, _sz, _vp, _sz, _vp, _sz, _vp]
         L.ezrs_kernel_path.argtypes = [_vp]
         L.ezrs_set_launch_rows.argtypes = [_vp, _sz]
         L.ezrs_set_semantics.argtypes = [_vp, _i]
@@ -199,6 +208,61 @@ def _stream_ptr(stream):
         import torch
         stream = torch.cuda.current_stream()
     return C.c_void_p(stream.cuda_stream) if hasattr(stream, "cuda_stream") else C.c_void_p(stream)
+
+
+def _shard_ptrs(seq, what, n, optional, device, w, shard_len=None):
+    """Validate a sequence of n 1-D contiguous device tensors of one length (None allowed at the
+    indices in `optional`); returns (host array of their device pointers, that length)."""
+    seq = list(seq)
+    if len(seq) != n:
+        raise EzrsError(f"{what}: {len(seq)} entries, expected {n}")
+    arr = (C.c_void_p * max(n, 1))()
+    for i, t in enumerate(seq):
+        if t is None:
+            if i not in optional:
+                raise EzrsError(f"{what}[{i}]: None where the call needs a buffer")
+            continue
+        if not getattr(t, "is_cuda", False):
+            raise EzrsError(f"{what}[{i}]: expected a GPU tensor")
+        if t.device.index != device:
+            raise EzrsError(f"{what}[{i}]: tensor on cuda:{t.device.index}, expected cuda:{device}")
+        if t.element_size() != w:
+            raise EzrsError(f"{what}[{i}]: expected {w}-byte elements, got {t.dtype}")
+        if t.dim() != 1 or (t.shape[0] > 1 and t.stride(0) != 1):
+            raise EzrsError(f"{what}[{i}]: expected a 1-D contiguous tensor")
+        if shard_len is None:
+            shard_len = t.shape[0]
+        elif t.shape[0] != shard_len:
+            raise EzrsError(f"{what}[{i}]: {t.shape[0]} symbols, the other shards have {shard_len}")
+        arr[i] = t.data_ptr()
+    return arr, (0 if shard_len is None else shard_len)
+
+
+def _ptr_table(t, what, need, device):
+    """Validate an int64 device tensor [nstripes, pitch >= need] with a contiguous last dimension;
+    returns (nstripes, pitch in entries)."""
+    import torch
+    if not getattr(t, "is_cuda", False):
+        raise EzrsError(f"{what}: expected a GPU tensor")
+    if t.device.index != device:
+        raise EzrsError(f"{what}: tensor on cuda:{t.device.index}, expected cuda:{device}")
+    if t.dtype != torch.int64:
+        raise EzrsError(f"{what}: expected int64 entries (device pointers), got {t.dtype}")
+    if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise EzrsError(f"{what}: expected a 2-D tensor [nstripes, pitch] with a contiguous last dimension")
+    if t.shape[1] < need:
+        raise EzrsError(f"{what}: {t.shape[1]} entries per stripe, the call needs {need}")
+    pitch = t.stride(0) if t.shape[0] > 1 else t.shape[1]
+    if pitch < need:
+        raise EzrsError(f"{what}: a stripe stride of {pitch} entries, the call needs {need}")
+    return t.shape[0], pitch
+
+
+def _align(align, w):
+    align = w if align is None else int(align)
+    if align not in (16, 4, w):
+        raise EzrsError(f"align: {align}, expected 16, 4 or the datum size {w}")
+    return align
 
 
 class Codec:
@@ -395,6 +459,42 @@ class Codec:
                                              _stream_ptr(stream)), "ezrs_decode_interleaved")
         return result
 
+    # -- pointer forms of the staged decode: every shard a buffer of its own ---------------------
+    def decode_ptrs_workspace_bytes(self, length, shard_len, nstripes):
+        return int(lib().ezrs_decode_ptrs_workspace_bytes(self._h, length, shard_len, nstripes))
+
+    def decode_ptrs(self, shards, length, eras=None, neras=None, result=None, positions=None,
+                    corr=None, stream=None):
+        """The pointer form of ``decode_interleaved`` (ezrs_decode_ptrs): one stripe.  shards:
+        length + nroots 1-D contiguous device tensors of equal length, by position (data first, then
+        parity); codeword j is symbol j of every shard and is decoded in place, errors and erasures.
+        Every shard is read and may be written; a lost shard is a tensor to rebuild into, its position
+        in every codeword's erasure list.  Returns the int32 result tensor [shard_len]."""
+        shards = list(shards)
+        arr, n = _shard_ptrs(shards, "shards", length + self.nroots, (), self.device,
+                             self.info.datum_bytes)
+        result, out = self._decode_out(n, eras, neras, result, positions, corr, like=shards[0])
+        _check(lib().ezrs_decode_ptrs(self._h, arr, length, n, *out, _stream_ptr(stream)),
+               "ezrs_decode_ptrs")
+        return result
+
+    def decode_ptrs_batch(self, table, length, shard_len, align=None, eras=None, neras=None,
+                          result=None, positions=None, corr=None, stream=None):
+        """The batched pointer form (ezrs_decode_ptrs_batch): table is the int64 device tensor
+        [nstripes, pitch >= length + nroots] of ``Recon.reconstruct_ptrs_batch`` (``ptr_table`` builds
+        one), every entry below length + nroots a buffer of shard_len symbols.  align: what every
+        pointer is a multiple of, 16, 4 or the datum size (None); a promise, not checked.  The table
+        is read while the kernels run.  Returns the int32 result tensor [nstripes * shard_len],
+        stripe-major."""
+        nstripes, pitch = _ptr_table(table, "table", length + self.nroots, self.device)
+        shard_len, align = int(shard_len), _align(align, self.info.datum_bytes)
+        if shard_len < 0:
+            raise EzrsError("shard_len: negative")
+        result, out = self._decode_out(nstripes * shard_len, eras, neras, result, positions, corr, like=table)
+        _check(lib().ezrs_decode_ptrs_batch(self._h, _tp(table), pitch, length, shard_len, nstripes, align,
+                                            *out, _stream_ptr(stream)), "ezrs_decode_ptrs_batch")
+        return result
+
     def recon_plan(self, length, lost):
         """Reconstruction plan for codewords of `length` data symbols whose symbols at the
         positions `lost` (relative to the first data symbol, parity at length..) are gone in
@@ -499,57 +599,13 @@ class _Plan:
                             "depth of at least 1")
 
     def _shard_ptrs(self, seq, what, n, optional, shard_len=None):
-        """Validate a sequence of n 1-D contiguous device tensors of one length (None allowed at the
-        indices in `optional`); returns (host array of their device pointers, that length)."""
-        seq = list(seq)
-        if len(seq) != n:
-            raise EzrsError(f"{what}: {len(seq)} entries, the plan has {n}")
-        arr = (C.c_void_p * max(n, 1))()
-        for i, t in enumerate(seq):
-            if t is None:
-                if i not in optional:
-                    raise EzrsError(f"{what}[{i}]: None where the call needs a buffer")
-                continue
-            if not getattr(t, "is_cuda", False):
-                raise EzrsError(f"{what}[{i}]: expected a GPU tensor")
-            if t.device.index != self.device:
-                raise EzrsError(f"{what}[{i}]: tensor on cuda:{t.device.index}, plan on cuda:{self.device}")
-            if t.element_size() != self._w:
-                raise EzrsError(f"{what}[{i}]: expected {self._w}-byte elements, got {t.dtype}")
-            if t.dim() != 1 or (t.shape[0] > 1 and t.stride(0) != 1):
-                raise EzrsError(f"{what}[{i}]: expected a 1-D contiguous tensor")
-            if shard_len is None:
-                shard_len = t.shape[0]
-            elif t.shape[0] != shard_len:
-                raise EzrsError(f"{what}[{i}]: {t.shape[0]} symbols, the other shards have {shard_len}")
-            arr[i] = t.data_ptr()
-        return arr, (0 if shard_len is None else shard_len)
-
+        return _shard_ptrs(seq, what, n, optional, self.device, self._w, shard_len)
 
     def _ptr_table(self, t, what, need):
-        """Validate an int64 device tensor [nstripes, pitch >= need] with a contiguous last dimension;
-        returns (nstripes, pitch in entries)."""
-        import torch
-        if not getattr(t, "is_cuda", False):
-            raise EzrsError(f"{what}: expected a GPU tensor")
-        if t.device.index != self.device:
-            raise EzrsError(f"{what}: tensor on cuda:{t.device.index}, plan on cuda:{self.device}")
-        if t.dtype != torch.int64:
-            raise EzrsError(f"{what}: expected int64 entries (device pointers), got {t.dtype}")
-        if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
-            raise EzrsError(f"{what}: expected a 2-D tensor [nstripes, pitch] with a contiguous last dimension")
-        if t.shape[1] < need:
-            raise EzrsError(f"{what}: {t.shape[1]} entries per stripe, the plan needs {need}")
-        pitch = t.stride(0) if t.shape[0] > 1 else t.shape[1]
-        if pitch < need:
-            raise EzrsError(f"{what}: a stripe stride of {pitch} entries, the plan needs {need}")
-        return t.shape[0], pitch
+        return _ptr_table(t, what, need, self.device)
 
     def _align(self, align):
-        align = self._w if align is None else int(align)
-        if align not in (16, 4, self._w):
-            raise EzrsError(f"align: {align}, expected 16, 4 or the datum size {self._w}")
-        return align
+        return _align(align, self._w)
 
 
 class Recon(_Plan):

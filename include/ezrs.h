@@ -410,6 +410,78 @@ int ezrs_update_ptrs_batch(const ezrs_update *plan, void *const *table, size_t t
                            const void *const *new_table, size_t new_pitch, size_t shard_len,
                            size_t nstripes, unsigned align, void *stream);
 
+/* Pointer forms of ezrs_decode_interleaved (device-resident): the error path of the pointer forms
+ * above.  A stripe whose verify or rebuild reported -1 holds errors at unknown positions; these
+ * calls decode it where it lies, errors and erasures, with no strided copy of the stripe.  Per
+ * stripe the call is exactly ezrs_decode_interleaved on one frame with depth = shard_len whose
+ * symbol row p is the buffer at position p (0 .. len+NROOTS-1, data first, then parity): codeword j
+ * is symbol j of every shard, and codewords are numbered stripe-major, k = s*shard_len + j, for
+ * result[k] and the rows k of eras / neras / positions / corr, which mean what they mean in
+ * ezrs_decode under both semantics of the codec and follow the same stride rules.
+ * Only the symbols of codewords whose result is nonzero are written (a -1 codeword carries the
+ * reference's partial corrections, rs_base:1610-1690); no other byte of any shard is touched.  The
+ * stripes are gathered into packed rows in the workspace, the codec's row kernels run on those and
+ * the rows of nonzero result are scattered back, a bounded number of codewords per pass.
+ *   ezrs_decode_ptrs         one stripe.  shards: a HOST array of len + NROOTS DEVICE pointers,
+ *            indexed by position, each shard_len symbols of the datum; read during the call and
+ *            not kept: the pointers travel by value as kernel arguments (into a table at the head of
+ *            the workspace), so the array is the caller's again when the call returns.  Every entry
+ *            is read and may be written, so none may be NULL: a lost shard still needs a buffer to be
+ *            rebuilt into, with that position in the codewords' erasure lists.  Symbols move as
+ *            dwords of four codewords when every pointer and shard_len are multiples of 4 (the OR of
+ *            the addresses, as in ezrs_reconstruct_ptrs), else one element at a time; any alignment
+ *            of the datum is valid.  Checked on the host before any launch.  -EINVAL: null codec,
+ *            `shards` or result; len outside 1..load; a NULL entry; shard_len * datum bytes
+ *            overflowing size_t; any two buffers overlapping over [p, p + shard_len * datum bytes);
+ *            the stride rules of ezrs_decode for eras, positions and corr when shard_len > 1; a
+ *            workspace that is too small.  -ENOTSUP: len + NROOTS above EZRS_PTRS_MAX.  shard_len
+ *            == 0 returns 0 and touches nothing.
+ *   ezrs_decode_ptrs_batch   nstripes stripes.  table: a DEVICE array of DEVICE pointers,
+ *            table[s*table_pitch + p] the shard at position p of stripe s, table_pitch >= len +
+ *            NROOTS, the entries from len + NROOTS up to table_pitch never read: the table of
+ *            ezrs_reconstruct_ptrs_batch, so one resident table serves verify, rebuild, update and
+ *            decode.  The kernels read it WHILE THEY RUN: it must stay valid and unchanged until the
+ *            work has completed on `stream`.  EZRS_PTRS_MAX does not apply.  align: the caller's
+ *            promise that every pointer of the table the call uses is a multiple of `align` bytes,
+ *            16, 4 or the size of the datum; the dword path is taken for align >= 4 and shard_len a
+ *            multiple of 4.  Checked on the host: -EINVAL for a null codec, `table` or result; len
+ *            outside 1..load; table_pitch < len + NROOTS; align not 16, 4 or the datum size;
+ *            shard_len * datum bytes or nstripes * shard_len overflowing size_t; the stride rules of
+ *            ezrs_decode when the call has more than one codeword; a workspace that is too small.
+ *            Otherwise nstripes == 0 or shard_len == 0 returns 0 and touches nothing.
+ *            NOT CHECKED, because the host cannot see the table, and undefined behaviour when
+ *            broken: a pointer that is not a multiple of `align`; a NULL (or invalid) entry at any
+ *            position below len + NROOTS; any overlap between two buffers of the call, in the same
+ *            stripe or in different stripes, or between a buffer and the table, each over [p, p +
+ *            shard_len * datum bytes).
+ * Asynchronous.  The forms without _ws use the calling stream's workspace (and may grow it, as
+ * ezrs_decode_interleaved does); the _ws forms take a caller-owned workspace of >=
+ * ezrs_decode_ptrs_workspace_bytes() bytes, allocate nothing and synchronise nothing.  That
+ * figure is what a call of either form uses for the geometry (0 for invalid arguments): one
+ * stripe's table, (len + NROOTS) pointers rounded up to 256 bytes, then
+ * ezrs_interleaved_workspace_bytes(codec, len, shard_len, nstripes). */
+size_t ezrs_decode_ptrs_workspace_bytes(const ezrs_codec *codec, unsigned len, size_t shard_len,
+                                        size_t nstripes);
+int ezrs_decode_ptrs(const ezrs_codec *codec, void *const *shards, unsigned len, size_t shard_len,
+                     const uint32_t *eras, size_t eras_stride, const uint32_t *neras,
+                     int32_t *result, uint32_t *positions, size_t pos_stride, void *corr,
+                     size_t corr_stride, void *stream);
+int ezrs_decode_ptrs_ws(const ezrs_codec *codec, void *const *shards, unsigned len,
+                        size_t shard_len, const uint32_t *eras, size_t eras_stride,
+                        const uint32_t *neras, int32_t *result, uint32_t *positions,
+                        size_t pos_stride, void *corr, size_t corr_stride, void *ws,
+                        size_t ws_bytes, void *stream);
+int ezrs_decode_ptrs_batch(const ezrs_codec *codec, void *const *table, size_t table_pitch,
+                           unsigned len, size_t shard_len, size_t nstripes, unsigned align,
+                           const uint32_t *eras, size_t eras_stride, const uint32_t *neras,
+                           int32_t *result, uint32_t *positions, size_t pos_stride, void *corr,
+                           size_t corr_stride, void *stream);
+int ezrs_decode_ptrs_batch_ws(const ezrs_codec *codec, void *const *table, size_t table_pitch,
+                              unsigned len, size_t shard_len, size_t nstripes, unsigned align,
+                              const uint32_t *eras, size_t eras_stride, const uint32_t *neras,
+                              int32_t *result, uint32_t *positions, size_t pos_stride, void *corr,
+                              size_t corr_stride, void *ws, size_t ws_bytes, void *stream);
+
 /* Host-memory forms: the same contracts with HOST pointers.  The batch is streamed through the
  * device in chunks of `chunk` codewords (0 = library default) over two HIP streams with
  * asynchronous copies; pinned host memory (ezrs_host_alloc) gets full PCIe overlap.  Blocking:

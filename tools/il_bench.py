@@ -10,7 +10,12 @@ every shape is warmed; interleaved and row-form calls alternate in the same proc
 repeats per figure sized so that each figure has at least 0.5 s of timed work; the figure is the
 median, the spread (max - min) / median.  The staged form is timed with the default staging chunk
 (EZRS_IL_STAGE_MB, inside the Infinity Cache) and with the whole batch staged in one pass.
-GB/s counts the frames' bytes once (ncw * 255)."""
+GB/s counts the frames' bytes once (ncw * 255).
+
+    python tools/il_bench.py --ptrs [--out profiles/il/il_ptrs_bench.json]
+
+The pointer forms of the staged decode (ezrs_decode_ptrs / ezrs_decode_ptrs_batch) against
+ezrs_decode_interleaved on the same symbols, same method: see ptrs_main."""
 import argparse
 import json
 import os
@@ -53,12 +58,99 @@ def figure(fns):
                 "iters": iters[n]} for n, v in runs.items()}
 
 
+# --ptrs: (name, codec, len, stripes, shard_len, align, one-stripe form)
+PTRS_SHAPES = [
+    ("RS(255,223) 1 x 1Mi a16", (255, 223), 223, 1, 1 << 20, 16, True),
+    ("RS(255,251) 10+4 1024 x 64Ki a16", (255, 251), 10, 1024, 1 << 16, 16, False),
+    ("RS(255,251) 10+4 1024 x 64Ki a1", (255, 251), 10, 1024, 1 << 16, 1, False),
+    ("RS(255,251) 10+4 64Ki x 256 a16", (255, 251), 10, 1 << 16, 256, 16, False),
+]
+
+
+def ptrs_main(out_path):
+    """The pointer forms of the staged decode against ezrs_decode_interleaved on the same symbols
+    laid out with sym_stride = shard_len: clean decode and decode with 1 % of the codewords
+    corrupted (one symbol each).  The corrupted figure times [put the corruption back, decode] in
+    both arms: a decode repairs its input, and the put is the same indexed store of 1 % of the
+    codewords' bytes into either layout.  Every shard is a buffer of its own, 16 bytes of gap to the
+    next; align 1 puts every shard at an odd address."""
+    out = {"reps": REPS, "device": torch.cuda.get_device_name(0), "results": []}
+    for name, (n, k), L, F, D, align, one in PTRS_SHAPES:
+        c = ezrs.Codec.rs(n, k)
+        S, ncw = L + c.nroots, F * D
+        g = torch.Generator(device="cuda").manual_seed(2)
+        fr = torch.randint(0, 256, (F, S, D), generator=g, device="cuda", dtype=torch.int32).to(torch.uint8)
+        c.encode_interleaved(fr)
+        pitch, off = D + 16, 0 if align == 16 else 1
+        arena = torch.zeros((F, S, pitch), dtype=torch.uint8, device="cuda")
+        arena[:, :, off:off + D] = fr
+        base = arena.data_ptr() + off
+        table = (base + torch.arange(F * S, dtype=torch.int64, device="cuda") * pitch).view(F, S)
+        shards = [arena[0, p, off:off + D] for p in range(S)] if one else None
+        res_p = torch.empty(ncw, dtype=torch.int32, device="cuda")
+        res_s = torch.empty(ncw, dtype=torch.int32, device="cuda")
+        # 1 % of the codewords, one wrong symbol each: flat indices into both layouts
+        nbad = max(1, ncw // 100)
+        kk = torch.randperm(ncw, generator=g, device="cuda")[:nbad]
+        pp = torch.randint(0, S, (nbad,), generator=g, device="cuda")
+        f, j = kk // D, kk % D
+        ix_s, ix_p = (f * S + pp) * D + j, (f * S + pp) * pitch + off + j
+        flat_s, flat_p = fr.view(-1), arena.view(-1)
+        wrong = flat_s[ix_s] ^ 0x5A
+
+        if one:
+            def dec_p():
+                c.decode_ptrs(shards, L, result=res_p)
+        else:
+            def dec_p():
+                c.decode_ptrs_batch(table, L, D, align=align, result=res_p)
+
+        def dec_s():
+            c.decode_interleaved(fr, result=res_s)
+
+        def bad_p():
+            flat_p[ix_p] = wrong
+            dec_p()
+
+        def bad_s():
+            flat_s[ix_s] = wrong
+            dec_s()
+
+        clean = figure({"ptrs": dec_p, "strided": dec_s})
+        torch.cuda.synchronize()
+        assert int((res_p != 0).sum()) == 0 and int((res_s != 0).sum()) == 0
+        bad = figure({"ptrs": bad_p, "strided": bad_s})
+        torch.cuda.synchronize()
+        assert int(res_p.sum()) == nbad == int(res_s.sum()) and torch.equal(res_p, res_s)
+        assert torch.equal(arena[:, :, off:off + D], fr)
+        for op, fg in (("decode_clean", clean), ("decode_1pct", bad)):
+            tp, ts = fg["ptrs"]["median_s"], fg["strided"]["median_s"]
+            rec = {"shape": name, "len": L, "nstripes": F, "shard_len": D, "align": align,
+                   "form": "ezrs_decode_ptrs" if one else "ezrs_decode_ptrs_batch", "op": op,
+                   "workspace_bytes": c.decode_ptrs_workspace_bytes(L, D, F),
+                   "t_ptrs_ms": tp * 1e3, "t_strided_ms": ts * 1e3, "ratio": tp / ts,
+                   "ptrs_GBps": ncw * S / tp / 1e9, "strided_GBps": ncw * S / ts / 1e9,
+                   "spread_ptrs": fg["ptrs"]["spread"], "spread_strided": fg["strided"]["spread"]}
+            out["results"].append(rec)
+            print(json.dumps(rec), flush=True)
+        del fr, arena, table, shards, res_p, res_s, flat_s, flat_p
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    with open(out_path, "w") as fh:
+        json.dump(out, fh, indent=1)
+    print("wrote", out_path)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ncw", type=int, default=1 << 20)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "il", "il_bench.json"))
+    ap.add_argument("--ptrs", action="store_true",
+                    help="the pointer forms of the staged decode against the strided form")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
     torch.cuda.set_device(0)
+    if args.ptrs:
+        return ptrs_main(args.out or os.path.join(ROOT, "profiles", "il", "il_ptrs_bench.json"))
+    args.out = args.out or os.path.join(ROOT, "profiles", "il", "il_bench.json")
     out = {"ncw": args.ncw, "reps": REPS, "device": torch.cuda.get_device_name(0), "results": []}
     for cname, mk in (("RS(255,223)", lambda: ezrs.Codec.rs(255, 223)),
                       ("RS_CCSDS(255,223)", lambda: ezrs.Codec.ccsds(223, True))):
