@@ -74,6 +74,16 @@ struct ezrs_update : FramePlan {
     std::vector<uint32_t> chg;          // host copy of the changed positions (the pointer form)
 };
 
+// A set of reconstruction plans of one codec geometry in one device allocation (ReconMixedArgs):
+// copies of the plans' tables behind a directory.  Const after ezrs_recon_set_create; it keeps
+// nothing of the plans it was made from.
+struct ezrs_recon_set {
+    int device = 0;
+    unsigned mm = 0, nroots = 0, len = 0;
+    unsigned nplans = 0, max_nlost = 0;
+    uint32_t *d_set = nullptr;
+};
+
 namespace {
 
 constexpr size_t kReconMaxTable = (size_t)64 << 20;   // bytes of a plan's device table (engine limit)
@@ -1012,6 +1022,101 @@ int ezrs_update_ptrs_batch(const ezrs_update *p, void *const *table, size_t tabl
     const DevTable t = table_view<const uint32_t>(p->d_tab, p->mm, p->nroots, p->nchg, p->nroots);
     hipError_t e = launch_update(a, nstripes, align, t, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return hip_fail(e, "update launch");
+    return 0;
+}
+
+// ---- mixed batched reconstruction: many stripes, a plan per stripe ---------------------------------
+int ezrs_recon_set_create(ezrs_recon_set **out, const ezrs_recon *const *plans, unsigned nplans) {
+    if (!out) return -EINVAL;
+    *out = nullptr;
+    auto bad = [](const char *what) {
+        g_last_error = std::string("reconstruction set: ") + what;
+        return -EINVAL;
+    };
+    if (!plans) return bad("null plans");
+    if (!nplans) return bad("no plans");
+    for (unsigned i = 0; i < nplans; ++i)
+        if (!plans[i]) return bad("a NULL plan");
+    const ezrs_recon *const p0 = plans[0];
+    for (unsigned i = 1; i < nplans; ++i)
+        if (plans[i]->mm != p0->mm || plans[i]->nroots != p0->nroots || plans[i]->len != p0->len ||
+            plans[i]->device != p0->device)
+            return bad("plans that differ in symbol bits, NROOTS, len or device");
+    // directory | images, each at a multiple of kReconSetAlign dwords
+    auto up = [](size_t w) { return (w + kReconSetAlign - 1) / kReconSetAlign * kReconSetAlign; };
+    const size_t cap = kReconMaxTable / sizeof(uint32_t), ent = sizeof(ReconSetEntry) / sizeof(uint32_t);
+    size_t words = nplans <= cap / ent ? up(nplans * ent) : cap + 1;
+    std::vector<ReconSetEntry> dir;
+    unsigned max_nlost = 0;
+    try {
+        for (unsigned i = 0; i < nplans && words <= cap; ++i) {
+            const ezrs_recon *p = plans[i];
+            dir.push_back({(uint32_t)words, p->nsurv, p->nlost,
+                           (uint32_t)(words + recon_coef_words(p->mm, p->nroots, p->nsurv))});
+            words += up(recon_table_words(p->mm, p->nroots, p->nsurv, p->nlost));
+            max_nlost = std::max(max_nlost, p->nlost);
+        }
+    } catch (const std::bad_alloc &) {
+        return -ENOMEM;
+    }
+    if (words > cap) {
+        g_last_error = "reconstruction set: device tables above 64 MiB together";
+        return -ENOTSUP;
+    }
+    ezrs_recon_set *s = new (std::nothrow) ezrs_recon_set;
+    if (!s) return -ENOMEM;
+    s->device = p0->device;
+    s->mm = p0->mm;
+    s->nroots = p0->nroots;
+    s->len = p0->len;
+    s->nplans = nplans;
+    s->max_nlost = max_nlost;
+    DeviceGuard g(s->device);
+    hipError_t e;
+    if ((e = hipMalloc(&s->d_set, words * sizeof(uint32_t))) != hipSuccess) {
+        delete s;
+        return hip_fail(e, "hipMalloc(reconstruction set)");
+    }
+    e = hipMemset(s->d_set, 0, words * sizeof(uint32_t));
+    if (e == hipSuccess)
+        e = hipMemcpy(s->d_set, dir.data(), dir.size() * sizeof(ReconSetEntry), hipMemcpyHostToDevice);
+    for (unsigned i = 0; i < nplans && e == hipSuccess; ++i) {
+        const ezrs_recon *p = plans[i];
+        e = hipMemcpy(s->d_set + dir[i].off, p->d_tab,
+                      recon_table_words(p->mm, p->nroots, p->nsurv, p->nlost) * sizeof(uint32_t),
+                      hipMemcpyDeviceToDevice);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);   // the plans may be destroyed at once
+    if (e != hipSuccess) {
+        ezrs_recon_set_destroy(s);
+        return hip_fail(e, "copy of the plans' tables (reconstruction set)");
+    }
+    *out = s;
+    return 0;
+}
+
+int ezrs_recon_set_destroy(ezrs_recon_set *s) {
+    if (!s) return 0;
+    DeviceGuard g(s->device);
+    if (s->d_set) (void)hipFree(s->d_set);
+    delete s;
+    return 0;
+}
+
+int ezrs_reconstruct_ptrs_mixed(const ezrs_recon_set *s, const uint32_t *plan_of, void *const *table,
+                                size_t table_pitch, size_t shard_len, size_t nstripes, unsigned align,
+                                int32_t *result, void *stream) {
+    if (!s || !plan_of || !table) return -EINVAL;
+    const size_t w = s->mm <= 8 ? 1 : 2;
+    if (int r = batch_check("reconstruct_ptrs_mixed", table_pitch, (size_t)s->len + s->nroots, shard_len,
+                            nstripes, align, w))
+        return r < 0 ? r : 0;
+    // nsurv, nlost: per stripe, from the directory
+    ReconMixedArgs a{{{{nullptr, 0, 0, shard_len, 0, 0, 0, 0}, result, 0, 0, s->mm, recon_row_pad(s->nroots),
+                       result ? s->nroots : s->max_nlost}, table, table_pitch, 0}, plan_of, s->d_set, s->nplans};
+    DeviceGuard g(s->device);
+    hipError_t e = launch_recon(a, nstripes, align, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "reconstruction launch");
     return 0;
 }
 

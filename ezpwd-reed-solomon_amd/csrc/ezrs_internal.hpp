@@ -305,6 +305,25 @@ struct UpdateBatchArgs : UpdateArgs {
     const void *const *new_table;
     size_t pitch, new_pitch, wruns;
 };
+// The mixed batched form (ezrs_reconstruct_ptrs_mixed): the batched form with a plan per stripe.
+// The plans of a set (ezrs_recon_set_create) lie in ONE device allocation, `set`, in dwords:
+//   directory [nplans] of ReconSetEntry | the plans' recon_table images, each at a multiple of
+//   kReconSetAlign dwords (what a plan's own allocation gives its table)
+// and stripe f of the call works under plan plan_of[f]; an index >= nplans skips the stripe.  What
+// ReconArgs says of one plan holds here for the whole set: nsurv and nlost are unused, and nrows is
+// nroots with a result, else the largest nlost of the set (the launcher's row block); a stripe
+// applies nroots rows or its own plan's nlost.
+struct ReconSetEntry {
+    uint32_t off;                 // of the plan's image, in dwords from `set`
+    uint32_t nsurv, nlost;
+    uint32_t pos;                 // of its survivor list: off + recon_coef_words(mm, nroots, nsurv)
+};
+constexpr size_t kReconSetAlign = 64;
+struct ReconMixedArgs : ReconBatchArgs {
+    const uint32_t *plan_of;      // [nstripes], device
+    const uint32_t *set;          // the directory is at its head
+    unsigned nplans;
+};
 // t: the plan's device table (table_view of its base).  The pointer forms: al is the OR of the
 // addresses in a.tab that the call uses; the batched forms: the alignment the caller promises for
 // every pointer of the tables.
@@ -314,5 +333,6 @@ hipError_t launch_recon(const ReconPtrArgs &a, size_t al, const DevTable &t, hip
 hipError_t launch_update(const UpdatePtrArgs &a, size_t al, const DevTable &t, hipStream_t s);
 hipError_t launch_recon(const ReconBatchArgs &a, size_t nstripes, size_t al, const DevTable &t, hipStream_t s);
 hipError_t launch_update(const UpdateBatchArgs &a, size_t nstripes, size_t al, const DevTable &t, hipStream_t s);
+hipError_t launch_recon(const ReconMixedArgs &a, size_t nstripes, size_t al, hipStream_t s);
 
 } // namespace ezrs

@@ -40,7 +40,9 @@
 // one base (the interleaved calls), one pointer per row, carried by value in the kernel arguments
 // (ezrs_reconstruct_ptrs / ezrs_update_ptrs: one stripe whose shards are buffers of their own), or
 // one pointer per row and stripe in a table in device memory (ezrs_reconstruct_ptrs_batch /
-// ezrs_update_ptrs_batch: many such stripes per call).
+// ezrs_update_ptrs_batch: many such stripes per call).  In the batch forms a wave never spans two
+// stripes, so all a plan contributes is uniform over the wave; ezrs_reconstruct_ptrs_mixed
+// (ReconMixedArgs) therefore chooses the plan per stripe, from a set of plans in one allocation.
 #include <algorithm>
 #include <cerrno>
 #include <new>
@@ -283,7 +285,8 @@ __device__ __forceinline__ void lane(const FrameSpan &a, size_t t, unsigned epl,
 template <class A>
 constexpr bool kTable = std::is_same_v<A, ReconPtrArgs> || std::is_same_v<A, UpdatePtrArgs>;
 template <class A>
-constexpr bool kBatch = std::is_same_v<A, ReconBatchArgs> || std::is_same_v<A, UpdateBatchArgs>;
+constexpr bool kBatch = std::is_same_v<A, ReconBatchArgs> || std::is_same_v<A, UpdateBatchArgs> ||
+                        std::is_same_v<A, ReconMixedArgs>;
 
 // The lane map of the batch forms.  A stripe takes a.wruns threads, its runs rounded up to a wave,
 // so a wave never spans two stripes: wave w of the launch works on stripe s = w / (wruns / 64) of
@@ -380,17 +383,17 @@ struct At {
 };
 
 // One survivor's dwords x into the accumulators of a row block; kp: its columns, bit b at
-// kp + b * nrp.  MB: the symbol bits when known at compile time (the bit loop is then unrolled and
+// kp + b * nrp (KP: a pointer to const uint32_t; in the constant address space for the mixed form).  MB: the symbol bits when known at compile time (the bit loop is then unrolled and
 // the columns' scalar loads are issued ahead), else 0 and mm is used.
 // bit + 0x7f.. is 0x80.. in the codewords whose bit is set and 0x7f.. in the others, i.e. the mask
 // 0xff.. / 0x00.. XOR the constant 0x7f..: one add instead of a shift and a subtract (which the
 // compiler turns into a quarter-rate multiply by 0xff).  What the constant adds to an accumulator,
 // XOR over all survivors and bits of K & 0x7f.., does not depend on the data: the table carries it
 // per row (`fix`) and the kernel takes it out once at the end.
-template <int RB, int ND, int MB>
-__device__ __forceinline__ void apply(const uint32_t (&x)[ND], const uint32_t *__restrict__ kp, unsigned nrp,
+template <int RB, int ND, int MB, class KP>
+__device__ __forceinline__ void apply(const uint32_t (&x)[ND], KP __restrict__ kp, unsigned nrp,
                                       unsigned mm, uint32_t ones, uint32_t low, uint32_t (&acc)[RB][ND]) {
-    auto bit = [&](unsigned b, const uint32_t *__restrict__ kb) {
+    auto bit = [&](unsigned b, KP __restrict__ kb) {
         uint32_t d[ND];
 #pragma unroll
         for (int i = 0; i < ND; ++i) d[i] = ((x[i] >> b) & ones) + low;
@@ -417,8 +420,8 @@ __device__ __forceinline__ void apply(const uint32_t (&x)[ND], const uint32_t *_
 // v_bitop3) per row and dword for m = 8, against eight v_bitop3 in the bit-column form, and five
 // shared instructions per dword instead of 24.  MB == 8: the three groups unrolled; else a loop
 // over the groups of mm bits, bits at and above mm masked out of the selectors.
-template <int RB, int ND, int MB>
-__device__ __forceinline__ void apply8(const uint32_t (&x)[ND], const uint32_t *__restrict__ kp, unsigned nrp,
+template <int RB, int ND, int MB, class KP>
+__device__ __forceinline__ void apply8(const uint32_t (&x)[ND], KP __restrict__ kp, unsigned nrp,
                                        unsigned mm, uint32_t (&acc)[RB][ND]) {
     if constexpr (MB == 8) {
         uint32_t i0[ND], i1[ND], i2[ND];
@@ -460,9 +463,9 @@ __device__ __forceinline__ void apply8(const uint32_t (&x)[ND], const uint32_t *
 
 // Two survivors of m = 8 symbols at once: their six lookups go into an accumulator with three
 // three-input XORs (two and a half instructions less per row and dword than one by one).
-template <int RB, int ND>
+template <int RB, int ND, class KP>
 __device__ __forceinline__ void apply8x2(const uint32_t (&x)[ND], const uint32_t (&y)[ND],
-                                         const uint32_t *__restrict__ kx, const uint32_t *__restrict__ ky,
+                                         KP __restrict__ kx, KP __restrict__ ky,
                                          unsigned nrp, uint32_t (&acc)[RB][ND]) {
     uint32_t ix[3][ND], iy[3][ND];
 #pragma unroll
@@ -493,11 +496,11 @@ __device__ __forceinline__ void apply8x2(const uint32_t (&x)[ND], const uint32_t
     }
 }
 
-// All survivors of the lane's run into the accumulators of the row block that starts at row r0:
-// kUnroll survivors' loads are issued together, the ragged end goes one by one.
-template <typename T, int RB, int V, int MB, class A>
-__device__ __forceinline__ void sweep(const At<T, A> &at, const uint32_t *__restrict__ K,
-                                      unsigned r0, const uint32_t *__restrict__ surv,
+// All nsurv survivors of the lane's run into the accumulators of the row block that starts at row
+// r0: kUnroll survivors' loads are issued together, the ragged end goes one by one.
+template <typename T, int RB, int V, int MB, class A, class KP>
+__device__ __forceinline__ void sweep(const At<T, A> &at, KP __restrict__ K,
+                                      unsigned r0, KP __restrict__ surv, unsigned nsurv,
                                       uint32_t (&acc)[RB][Run<T, V>::ND]) {
     using R = Run<T, V>;
     const A &a = at.a;
@@ -511,7 +514,7 @@ __device__ __forceinline__ void sweep(const At<T, A> &at, const uint32_t *__rest
         else apply<RB, ND, MB>(x, K + c * kstep, a.nrp, mm, 0x00010001u, 0x7fff7fffu, acc);
     };
     unsigned c = 0;
-    for (; c + kUnroll <= a.nsurv; c += kUnroll) {
+    for (; c + kUnroll <= nsurv; c += kUnroll) {
         uint32_t x[kUnroll][ND];
 #pragma unroll
         for (unsigned u = 0; u < kUnroll; ++u) R::load(at.row(surv[c + u], c + u), x[u]);
@@ -524,14 +527,21 @@ __device__ __forceinline__ void sweep(const At<T, A> &at, const uint32_t *__rest
             for (unsigned u = 0; u < kUnroll; ++u) one(x[u], c + u);
         }
     }
-    for (; c < a.nsurv; ++c) {
+    for (; c < nsurv; ++c) {
         uint32_t x[ND];
         R::load(at.row(surv[c], c), x);
         one(x, c);
     }
 }
 
-// K: the coefficients; surv / lost: the positions; fix: [nrp] (recon_table).
+// K: the coefficients; surv / lost: the positions; fix: [nrp] (recon_table).  The mixed form
+// (ReconMixedArgs) gets four null pointers and takes all of that per stripe: the stripe f is uniform
+// over the wave (batch_lane), so its plan index, the plan's directory entry and from there the four
+// parts of the plan's image are dependent scalar loads at the top of the wave; they are read through
+// the constant address space, as At::Slot is (nothing the call writes may overlap plan_of or the
+// set), and what follows from them stays in scalar registers.  A stripe whose index names no plan
+// returns before anything is asked of the pointer table.  RB serves the whole set; the block loop
+// runs to the stripe's own rows.
 template <typename T, int RB, int V, class A>
 __global__ void __launch_bounds__(256) k_recon(A a, const uint32_t *__restrict__ K,
                                                const uint32_t *__restrict__ surv,
@@ -546,30 +556,52 @@ __global__ void __launch_bounds__(256) k_recon(A a, const uint32_t *__restrict__
     const At<T, A> at(a, t, R::EPL);
     if constexpr (kBatch<A>)                        // nothing has been asked for yet
         if (!at.live) return;
+    unsigned nsurv = a.nsurv, nlost = a.nlost, nrows = a.nrows;
+    constexpr bool MIXED = std::is_same_v<A, ReconMixedArgs>;
+    typedef __attribute__((address_space(4))) const uint32_t Word;
+    std::conditional_t<MIXED, Word *, const uint32_t *> Kt, st, lt, ft;   // the plan's table, by part
+    if constexpr (MIXED) {
+        const uint32_t pi = __builtin_amdgcn_readfirstlane(((Word *)a.plan_of)[at.f]);
+        if (pi >= a.nplans) return;
+        Word *const set = (Word *)a.set, *const ent = set + (size_t)pi * (sizeof(ReconSetEntry) / 4);
+        nsurv = ent[1];
+        nlost = ent[2];
+        if (!a.result) nrows = nlost;
+        if (!nrows) return;
+        Kt = set + ent[0];
+        st = set + ent[3];
+        lt = st + nsurv;
+        ft = lt + nlost;
+    } else {
+        Kt = K;
+        st = surv;
+        lt = lost;
+        ft = fix;
+    }
     uint32_t bad[ND];
 #pragma unroll
     for (int d = 0; d < ND; ++d) bad[d] = 0;
-    for (unsigned r0 = 0; r0 < a.nrows; r0 += RB) {
+    for (unsigned r0 = 0; r0 < nrows; r0 += RB) {
         uint32_t acc[RB][ND];
 #pragma unroll
         for (int r = 0; r < RB; ++r)
 #pragma unroll
             for (int d = 0; d < ND; ++d) acc[r][d] = 0;
-        if (a.mm == 8) sweep<T, RB, V, 8>(at, K, r0, surv, acc);
-        else sweep<T, RB, V, 0>(at, K, r0, surv, acc);
+        if (a.mm == 8) sweep<T, RB, V, 8>(at, Kt, r0, st, nsurv, acc);
+        else sweep<T, RB, V, 0>(at, Kt, r0, st, nsurv, acc);
 #pragma unroll
         for (int r = 0; r < RB; ++r) {
             const unsigned row = r0 + r;
-            const uint32_t fx = fix[row];
+            const uint32_t fx = ft[row];
 #pragma unroll
             for (int d = 0; d < ND; ++d) acc[r][d] ^= fx;
-            if (row < a.nlost) {
+            if (row < nlost) {
                 if constexpr (kTable<A>) {          // a null entry: that shard is not wanted
-                    if (at.entry(a.nsurv + row)) R::store(at.row(0, a.nsurv + row), acc[r]);
+                    if (at.entry(nsurv + row)) R::store(at.row(0, nsurv + row), acc[r]);
                 } else if constexpr (kBatch<A>) {   // ... by this stripe
-                    if (at.slot(lost[row])) R::store(at.row(lost[row], 0), acc[r]);
+                    if (at.slot(lt[row])) R::store(at.row(lt[row], 0), acc[r]);
                 } else {
-                    R::store(at.row(lost[row], 0), acc[r]);
+                    R::store(at.row(lt[row], 0), acc[r]);
                 }
             } else {                                // check rows; the padding rows are zero
 #pragma unroll
@@ -585,7 +617,7 @@ __global__ void __launch_bounds__(256) k_recon(A a, const uint32_t *__restrict__
 #pragma unroll
             for (unsigned e = 0; e < EPD; ++e) {
                 const uint32_t v = V ? (bad[d] >> (W * e)) & ((1u << W) - 1u) : bad[d];
-                res[d * EPD + e] = v ? -1 : (int32_t)a.nlost;
+                res[d * EPD + e] = v ? -1 : (int32_t)nlost;
             }
     }
 }
@@ -904,6 +936,9 @@ hipError_t launch_recon(const ReconBatchArgs &a, size_t nstripes, size_t al, con
 }
 hipError_t launch_update(const UpdateBatchArgs &a, size_t nstripes, size_t al, const DevTable &t, hipStream_t s) {
     return update_any(a, nstripes, al, t, s);
+}
+hipError_t launch_recon(const ReconMixedArgs &a, size_t nstripes, size_t al, hipStream_t s) {
+    return recon_any(a, nstripes, al, DevTable{}, s);   // !a.nrows: no result and no plan that rebuilds
 }
 
 } // namespace ezrs

@@ -112,6 +112,9 @@ def lib():
         L.ezrs_update_ptrs.argtypes = [_vp, _vp, _vp, _sz, _vp]
         L.ezrs_reconstruct_ptrs_batch.argtypes = [_vp, _vp, _sz, _sz, _sz, _u, _vp, _vp]
         L.ezrs_update_ptrs_batch.argtypes = [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _u, _vp]
+        L.ezrs_recon_set_create.argtypes = [C.POINTER(_vp), _vp, _u]
+        L.ezrs_recon_set_destroy.argtypes = [_vp]
+        L.ezrs_reconstruct_ptrs_mixed.argtypes = [_vp, _vp, _vp, _sz, _sz, _sz, _u, _vp, _vp]
         L.ezrs_decode_ptrs_workspace_bytes.restype = _sz
         L.ezrs_decode_ptrs_workspace_bytes.argtypes = [_vp, _u, _sz, _sz]
         L.ezrs_decode_ptrs.argtypes = [_vp, _vp, _u, _sz, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _sz, _vp]
@@ -677,6 +680,60 @@ class Recon(_Plan):
         _check(lib().ezrs_reconstruct_ptrs_batch(self._h, _tp(table), pitch, shard_len, nstripes, align,
                                                  _tp(result), _stream_ptr(stream)),
                "ezrs_reconstruct_ptrs_batch")
+        return result
+
+
+PLAN_SKIP = 0xFFFFFFFF                             # EZRS_PLAN_SKIP: in plan_of, leave this stripe alone
+
+
+class ReconSet(_Plan):
+    """A set of reconstruction plans of one codec, length and device (ezrs_recon_set_create), for
+    ``reconstruct_ptrs_mixed``: the batched pointer form with a loss pattern per stripe.  The set
+    copies the plans' tables; it keeps nothing of the plans or the codec.
+
+    * ``nplans``  the number of plans; an index at or above it (``PLAN_SKIP``) skips a stripe
+    * ``nlost``   the plans' nlost, by index: what ``result`` holds for a stripe of that plan, or -1"""
+
+    _destroy = "ezrs_recon_set_destroy"
+
+    def __init__(self, plans):
+        plans = list(plans)
+        for i, p in enumerate(plans):
+            if not isinstance(p, Recon) or not p._h:
+                raise EzrsError(f"plans[{i}]: expected a Recon plan")
+        self.nplans, self.nlost = len(plans), [p.nlost for p in plans]
+        arr = (_vp * max(len(plans), 1))(*[p._h for p in plans])
+        h = _vp()
+        self._h = None
+        _check(lib().ezrs_recon_set_create(C.byref(h), arr, len(plans)), "ezrs_recon_set_create")
+        self._h = h
+        self.length, self.nroots, self.device, self._w = (plans[0].length, plans[0].nroots, plans[0].device,
+                                                          plans[0]._w)
+
+    def reconstruct_ptrs_mixed(self, table, plan_of, shard_len, align=None, result=None, stream=None):
+        """ezrs_reconstruct_ptrs_mixed: table, shard_len, align, result and stream as in
+        ``Recon.reconstruct_ptrs_batch``; plan_of: an int32 or uint32 device tensor of at least
+        nstripes entries, stripe s working under plan plan_of[s] of the set (0 in the table where
+        that plan has lost a position: not wanted by that stripe).  A stripe whose index is not
+        below ``nplans`` is skipped: nothing of it is read or written, and its result entries stay.
+        The table and plan_of are read while the kernels run.  Returns result."""
+        import torch
+        nstripes, pitch = self._ptr_table(table, "table", self.length + self.nroots)
+        shard_len, align = int(shard_len), self._align(align)
+        if shard_len < 0:
+            raise EzrsError("shard_len: negative")
+        _dev_rows(plan_of, "plan_of", self.device, 4, ndim=1)
+        if plan_of.dtype not in (torch.int32, torch.uint32):
+            raise EzrsError(f"plan_of: expected int32 or uint32 entries, got {plan_of.dtype}")
+        if plan_of.shape[0] < nstripes:
+            raise EzrsError("plan_of: fewer entries than stripes")
+        if result is not None:
+            _dev_rows(result, "result", self.device, 4, ndim=1)
+            if result.shape[0] < nstripes * shard_len:
+                raise EzrsError("result: fewer entries than codewords")
+        _check(lib().ezrs_reconstruct_ptrs_mixed(self._h, _tp(plan_of), _tp(table), pitch, shard_len, nstripes,
+                                                 align, _tp(result), _stream_ptr(stream)),
+               "ezrs_reconstruct_ptrs_mixed")
         return result
 
 

@@ -410,6 +410,52 @@ int ezrs_update_ptrs_batch(const ezrs_update *plan, void *const *table, size_t t
                            const void *const *new_table, size_t new_pitch, size_t shard_len,
                            size_t nstripes, unsigned align, void *stream);
 
+/* Mixed-plan batched reconstruction (device-resident): ezrs_reconstruct_ptrs_batch with a loss
+ * pattern per stripe, for the sweeps in which one plan does not fit all stripes: a rebuild under
+ * rotated placement (the failed drive holds another position of every stripe), a scrub that meets
+ * healthy stripes (nlost == 0: verify) next to degraded ones, new stripes that want the all-parity
+ * plan (encode) among them.  One call on the resident table, with no bucketing by pattern on the
+ * host, no compacted table per bucket and no launch per bucket.
+ *   ezrs_recon_set_create   gathers nplans existing plans into one device allocation on the plans'
+ *            device: a directory (per plan: where its table lies, nsurv, nlost) and copies of the
+ *            plans' device tables back to back.  The set copies what it needs and may synchronise
+ *            to do so; it stays valid after the plans and the codec are destroyed, is const
+ *            afterwards and may be shared by threads and streams.  The same pattern may appear
+ *            more than once.  -EINVAL, before any device is touched: null `out` or `plans`; nplans
+ *            == 0; a NULL entry; plans that differ in symbol bits, NROOTS, len or device.  -ENOTSUP:
+ *            the set's allocation would exceed 64 MiB (the limit of one plan's table, here for the
+ *            directory and all tables together).  -ENOMEM; -EIO for a HIP failure.  Plans of
+ *            different codecs with equal symbol bits, NROOTS and len are NOT detected: each stripe
+ *            simply gets its plan's matrix.
+ *   ezrs_reconstruct_ptrs_mixed   stripe s works under plan plan_of[s] of the set.  plan_of: a DEVICE
+ *            array of nstripes indices on the set's device, read WHILE THE KERNELS RUN, like the
+ *            table.  Per stripe the call is exactly ezrs_reconstruct_ptrs_batch under that stripe's
+ *            plan: the same bytes are written; result[s*shard_len + j] is that plan's nlost, or -1;
+ *            NULL at a lost position of that stripe's plan means "not wanted" for that stripe;
+ *            table, table_pitch, align and the ragged end of shard_len mean what they mean there.
+ *            An index >= nplans skips the stripe (EZRS_PLAN_SKIP is the named way to say so): none
+ *            of its table entries are read, so they may be anything, no byte of any shard is
+ *            written, and its `result` entries are left as they were.  With result == NULL only the
+ *            rebuild rows of each stripe's own plan are applied; a stripe whose plan has nlost == 0
+ *            then does nothing, and none of its table entries are read either.
+ *            Asynchronous; no workspace; never allocates, never synchronises; capturable.
+ * NOT CHECKED, and undefined behaviour when broken: what ezrs_reconstruct_ptrs_batch lists, for
+ * every stripe that is not skipped under that stripe's plan, and any overlap between a buffer the
+ * call writes (`result` included) and plan_of.
+ * Checked on the host before any launch.  -EINVAL: null set, plan_of or `table`; table_pitch < len +
+ * NROOTS; align not 16, 4 or the datum size; shard_len * datum bytes or nstripes * shard_len
+ * overflowing size_t.  Otherwise nstripes == 0 or shard_len == 0 returns 0 and touches nothing.
+ * The strided form and the update forms have no mixed variant: in the strided lane map a wave may
+ * span two frames, so a plan per frame would not be uniform over a wave, and update plans differ per
+ * stripe in the changed positions and in the rows of new_table. */
+typedef struct ezrs_recon_set ezrs_recon_set;
+#define EZRS_PLAN_SKIP 0xFFFFFFFFu   /* in plan_of: leave this stripe alone */
+int ezrs_recon_set_create(ezrs_recon_set **out, const ezrs_recon *const *plans, unsigned nplans);
+int ezrs_recon_set_destroy(ezrs_recon_set *set);   /* NULL: 0 */
+int ezrs_reconstruct_ptrs_mixed(const ezrs_recon_set *set, const uint32_t *plan_of,
+                                void *const *table, size_t table_pitch, size_t shard_len,
+                                size_t nstripes, unsigned align, int32_t *result, void *stream);
+
 /* Pointer forms of ezrs_decode_interleaved (device-resident): the error path of the pointer forms
  * above.  A stripe whose verify or rebuild reported -1 holds errors at unknown positions; these
  * calls decode it where it lies, errors and erasures, with no strided copy of the stripe.  Per

@@ -6,6 +6,7 @@ per-codeword check) against the staged decode given the same erasures in every c
     python tools/recon_bench.py [--gib 1.0] [--out profiles/recon/recon_bench.json]
     python tools/recon_bench.py --ptrs [--gib 1.0] [--out profiles/recon/recon_ptrs_bench.json]
     python tools/recon_bench.py --batch [--gib 1.0] [--out profiles/recon/recon_batch_bench.json]
+    python tools/recon_bench.py --mixed [--gib 1.0] [--out profiles/recon/recon_mixed_bench.json]
 
 One frame per shape: len + nroots shards of `depth` symbols, symbol stride = depth, sized so that
 the frame holds at least --gib GiB (well past the 256 MiB Infinity Cache).  Device events; every
@@ -38,7 +39,23 @@ permutation, so addresses are monotonic neither in the position nor in the strip
   batch_inframe  the batch call on a table of pointers to the rows of the strided frames
            themselves: the same addresses as the strided call, so that the kernels' addressing is
            compared apart from where the shards lie
-batch_over_loop, batch_over_strided and inframe_over_strided are the ratios of the medians."""
+batch_over_loop, batch_over_strided and inframe_over_strided are the ratios of the medians.
+
+--mixed: the single-drive rebuild of rotated placement, RS(255,251) shortened to len 10 (14 shards
+per stripe), shards of 4 KiB and of 64 KiB, stripe s having lost position s % 14; with and without
+`result`.  The shards lie as in --batch; the table of all stripes is resident.  Alternating:
+  buckets    what a caller without the mixed call does: 14 ezrs_reconstruct_ptrs_batch calls, one per
+             pattern, on 14 compacted tables.  The bucketing, the sub-tables and the per-bucket
+             result buffers are built outside the timed region, which favours this way
+  mixed      one ezrs_reconstruct_ptrs_mixed call on the resident table, plan_of[s] = s % 14
+  batch_one  one ezrs_reconstruct_ptrs_batch call on the resident table under the plan that has lost
+             position 0: as many stripes, one plan, the ceiling
+  mixed_one  the mixed call with a set of that one plan and plan_of all zero: the same work as
+             batch_one, through the directory
+  batch_one_again  batch_one a second time in the alternation: how far two timings of the same call
+             lie apart in this run
+mixed_over_buckets, mixed_over_batch_one, mixed_one_over_batch_one and batch_again_over_batch_one are
+the ratios of the medians; the spreads of the figures are next to them."""
 import ctypes as C
 import argparse
 import json
@@ -232,17 +249,111 @@ def main_batch(args):
     return out
 
 
+MIXED_SHARD_BYTES = [4 << 10, 64 << 10]
+
+
+def main_mixed(args):
+    L, sp = ezrs.lib(), ezrs._stream_ptr(None)
+    out = {"gib": args.gib, "reps": REPS, "device": torch.cuda.get_device_name(0), "results": []}
+    name, length = "RS(255,251) len 10, stripe s lost [s % 14]", 10
+    for use_result in (True, False):
+        for n in MIXED_SHARD_BYTES:                 # 1-byte symbols
+            c = ezrs.Codec.rs(255, 251)
+            S = length + c.nroots
+            ns = max(S, -(-int(args.gib * (1 << 30)) // (S * n)))
+            frames = torch.empty((ns, S, n), dtype=torch.uint8, device="cuda")
+            g = torch.Generator(device="cuda").manual_seed(1)
+            step = max(1, (64 << 20) // (length * n))           # 64 Mi symbols at a time
+            for s0 in range(0, ns, step):
+                blk = frames[s0:s0 + step, :length]
+                blk.copy_(torch.randint(0, 256, blk.shape, generator=g, device="cuda", dtype=torch.uint8))
+            c.recon_plan(length, list(range(length, S))).reconstruct(frames)    # the parity
+            perm = torch.randperm(ns * S, generator=torch.Generator().manual_seed(2))
+            pool = torch.empty((ns * S, n), dtype=torch.uint8, device="cuda")
+            pool[perm.cuda()] = frames.view(ns * S, n)
+            good = pool.clone()
+            del frames
+            table = (pool.data_ptr() + perm.view(ns, S) * n).cuda()     # [ns, S] int64, resident
+            assert pool.data_ptr() % 16 == 0
+            plan_of = (torch.arange(ns, dtype=torch.int32) % S).cuda()
+            lost_slots = perm.view(ns, S)[torch.arange(ns), torch.arange(ns) % S].cuda()   # slot of (s, s % S)
+            first_slots = perm.view(ns, S)[:, 0].contiguous().cuda()                       # slot of (s, 0)
+            plans = [c.recon_plan(length, [k]) for k in range(S)]
+            rset, rset1 = ezrs.ReconSet(plans), ezrs.ReconSet(plans[:1])
+            zeros = torch.zeros(ns, dtype=torch.int32, device="cuda")
+            # the parent's way, prepared: per pattern the compacted table and a result buffer
+            sub = [table[k::S].contiguous() for k in range(S)]
+            res = torch.empty(ns * n, dtype=torch.int32, device="cuda") if use_result else None
+            sub_res = [torch.empty(t.shape[0] * n, dtype=torch.int32, device="cuda") if use_result else None
+                       for t in sub]
+            rp = res.data_ptr() if use_result else None
+            calls = [(plans[k]._h, sub[k].data_ptr(), sub[k].shape[0], sub_res[k].data_ptr() if use_result else None)
+                     for k in range(S)]
+
+            def buckets():
+                for h, t, nb, r in calls:
+                    L.ezrs_reconstruct_ptrs_batch(h, t, S, n, nb, 16, r, sp)
+
+            def batch_one():
+                return L.ezrs_reconstruct_ptrs_batch(plans[0]._h, table.data_ptr(), S, n, ns, 16, rp, sp)
+
+            fns = {"buckets": buckets,
+                   "mixed": lambda: L.ezrs_reconstruct_ptrs_mixed(rset._h, plan_of.data_ptr(), table.data_ptr(), S, n,
+                                                                  ns, 16, rp, sp),
+                   "batch_one": batch_one,
+                   "mixed_one": lambda: L.ezrs_reconstruct_ptrs_mixed(rset1._h, zeros.data_ptr(), table.data_ptr(), S,
+                                                                      n, ns, 16, rp, sp),
+                   "batch_one_again": lambda: batch_one()}
+            for what, fn in fns.items():            # each path once on garbage
+                pool[first_slots if "one" in what else lost_slots] = 0x5A
+                if use_result:
+                    res.fill_(77)
+                    for r in sub_res:
+                        r.fill_(77)
+                r = fn()
+                assert r is None or r == 0, (n, what)
+                torch.cuda.synchronize()
+                assert torch.equal(pool, good), (n, what)
+                if use_result:
+                    for r in sub_res if what == "buckets" else [res]:
+                        assert bool((r == 1).all()), (n, what)
+            fg = figure(fns)
+            torch.cuda.synchronize()
+            assert torch.equal(pool, good), n
+            rec = {"shape": name, "len": length, "nroots": c.nroots, "shard_bytes": n, "nstripes": ns,
+                   "total_bytes": ns * S * n, "result": use_result}
+            for k, v in fg.items():
+                rec[f"t_{k}_ms"], rec[f"spread_{k}"] = v["median_s"] * 1e3, v["spread"]
+                rec[f"{k}_GBps"] = ns * S * n / v["median_s"] / 1e9
+            med = {k: v["median_s"] for k, v in fg.items()}
+            rec["mixed_over_buckets"] = med["mixed"] / med["buckets"]
+            rec["mixed_over_batch_one"] = med["mixed"] / med["batch_one"]
+            rec["mixed_one_over_batch_one"] = med["mixed_one"] / med["batch_one"]
+            rec["batch_again_over_batch_one"] = med["batch_one_again"] / med["batch_one"]
+            rec["iters"] = {k: v["iters"] for k, v in fg.items()}
+            out["results"].append(rec)
+            print(json.dumps(rec), flush=True)
+            del good, pool, table, sub, res, sub_res, plans, rset, rset1, c, fns, calls, lost_slots, first_slots
+            torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gib", type=float, default=1.0)
     ap.add_argument("--ptrs", action="store_true", help="the pointer form against the strided form")
     ap.add_argument("--batch", action="store_true", help="many small stripes: loop, batch call, strided call")
+    ap.add_argument("--mixed", action="store_true",
+                    help="rotated placement: a call per pattern, one mixed call, one single-plan call")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     args.out = args.out or os.path.join(ROOT, "profiles", "recon",
+                                        "recon_mixed_bench.json" if args.mixed else
                                         "recon_batch_bench.json" if args.batch else
                                         "recon_ptrs_bench.json" if args.ptrs else "recon_bench.json")
     torch.cuda.set_device(0)
+    if args.mixed:
+        return write(args.out, main_mixed(args))
     if args.batch:
         return write(args.out, main_batch(args))
     if args.ptrs:
