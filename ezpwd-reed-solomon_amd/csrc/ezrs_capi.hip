@@ -642,14 +642,21 @@ size_t il_ptrs_head(size_t positions) { return (positions * sizeof(void *) + 255
 //   encode (dec == null): gather the data symbols, scatter the parity symbols of every codeword
 //   decode: gather whole codewords, scatter whole rows of the codewords whose result is nonzero
 // pt != null: the frames are named by pointers (`frames` is null, depth the shard length).
+// sl != null (a decode): the selection policy.  ncw then counts the rows of sl->sel, which are what
+// the passes, the workspace and the outputs follow; the codewords they name are sl->ncw.
+struct IlSelect {
+    const uint64_t *sel, *count;
+    size_t ncw;
+};
+
 int il_run(const ezrs_codec *c, void *frames, size_t frame_pitch, size_t sym_stride, size_t depth,
            unsigned len, size_t ncw, const DecodeOut *dec, const CallerWs *cw, void *stream,
-           const IlPtrs *pt = nullptr) {
+           const IlPtrs *pt = nullptr, const IlSelect *sl = nullptr) {
     DeviceGuard g(c->device);
     void *ws = nullptr;
     const unsigned NR = c->dev.nroots;
     const size_t w = sym_bytes(c->dev), P = (size_t)len + NR;
-    const size_t head = pt ? il_ptrs_head(P) : 0;
+    const size_t head = pt && !sl ? il_ptrs_head(P) : 0;
     if (int r = take_ws(c, cw, head + il_ws_bytes(c, len, ncw), stream, &ws)) return r;
     hipStream_t st = static_cast<hipStream_t>(stream);
     void *const *table = pt ? pt->table : nullptr;
@@ -665,7 +672,10 @@ int il_run(const ezrs_codec *c, void *frames, size_t frame_pitch, size_t sym_str
         const size_t n = ncw - k0 < chunk ? ncw - k0 : chunk;
         IlPtrArgs a{{frames, frame_pitch, sym_stride, depth, stage, P, k0, (uint32_t)n, 0, dec ? len + NR : len,
                      nullptr}, table, pt ? pt->pitch : 0};
-        hipError_t e = pt ? launch_il_gather(c->dev, a, pt->al, st) : launch_il_gather(c->dev, (const IlArgs &)a, st);
+        IlSel<IlPtrArgs> as{a, sl ? sl->sel : nullptr, sl ? sl->count : nullptr, sl ? sl->ncw : 0};
+        hipError_t e = sl   ? launch_il_gather(c->dev, as, pt != nullptr, st)
+                       : pt ? launch_il_gather(c->dev, a, pt->al, st)
+                            : launch_il_gather(c->dev, (const IlArgs &)a, st);
         if (e != hipSuccess) return hip_fail(e, "interleaved gather launch");
         if (!dec) {
             if (int r = run_encode(c, EncodeArgs{stage, P, len, stage + (size_t)len * w, P, n}, ws, stream))
@@ -675,9 +685,11 @@ int il_run(const ezrs_codec *c, void *frames, size_t frame_pitch, size_t sym_str
         } else {
             if (int r = run_decode(c, dec->args(c, stage, P, len, stage + (size_t)len * w, P, k0, n), ws, stream))
                 return r;
-            a.result = dec->result + k0;
+            a.result = as.result = dec->result + k0;
         }
-        e = pt ? launch_il_scatter(c->dev, a, pt->al, st) : launch_il_scatter(c->dev, (const IlArgs &)a, st);
+        e = sl   ? launch_il_scatter(c->dev, as, pt != nullptr, st)
+            : pt ? launch_il_scatter(c->dev, a, pt->al, st)
+                 : launch_il_scatter(c->dev, (const IlArgs &)a, st);
         if (e != hipSuccess) return hip_fail(e, "interleaved scatter launch");
     }
     return 0;
@@ -1205,6 +1217,115 @@ int ezrs_decode_ptrs_batch_ws(const ezrs_codec *c, void *const *table, size_t ta
     return decode_ptrs_batch(c, table, table_pitch, len, shard_len, nstripes, align,
                              {eras, eras_stride, neras, result, positions, pos_stride, corr, corr_stride}, &cw,
                              stream);
+}
+
+// ---- selection: the failed codewords of a verify, and a decode of only those -----------------------
+namespace {
+
+// ezrs_select_failed(_ws): cw == null uses the stream's workspace.
+int select_failed(const ezrs_codec *c, const int32_t *result, size_t n, uint64_t base, uint64_t *sel, size_t cap,
+                  uint64_t *count, const CallerWs *cw, void *stream) {
+    if (!c || !sel || !count || (n && !result)) return -EINVAL;
+    if (n && base > UINT64_MAX - n) return -EINVAL;
+    DeviceGuard g(c->device);
+    void *ws = nullptr;
+    if (int r = take_ws(c, cw, select_ws_bytes(n), stream, &ws)) return r;
+    hipError_t e = launch_select_failed(result, n, base, sel, cap, count, ws, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : hip_fail(e, "selection launch");
+}
+
+// ezrs_decode_ptrs_select(_ws): rows of `sel` over the table of ezrs_decode_ptrs_batch.
+int decode_ptrs_select(const ezrs_codec *c, void *const *table, size_t table_pitch, unsigned len,
+                       size_t shard_len, size_t nstripes, const uint64_t *sel, size_t nsel, const uint64_t *count,
+                       const DecodeOut &o, const CallerWs *cw, void *stream) {
+    if (!c) return -EINVAL;
+    if (nsel == 0) return 0;
+    if (!table || !sel || !o.result) return -EINVAL;
+    if (len < 1 || len > c->dev.load) return -EINVAL;
+    const unsigned w = sym_bytes(c->dev);
+    if (int r = batch_check("decode_ptrs_select", table_pitch, (size_t)len + c->dev.nroots, shard_len, nstripes, w, w))
+        return r < 0 ? r : 0;
+    if (int r = check_decode_out(c, nsel, o)) return r;
+    const IlPtrs pt{table, table_pitch, w, nullptr};
+    const IlSelect sl{sel, count, nstripes * shard_len};
+    return il_run(c, nullptr, 0, 0, shard_len, len, nsel, &o, cw, stream, &pt, &sl);
+}
+
+// ezrs_decode_interleaved_select(_ws): rows of `sel` over the frames of ezrs_decode_interleaved.
+int decode_il_select(const ezrs_codec *c, void *frames, size_t frame_pitch, size_t sym_stride, size_t depth,
+                     unsigned len, size_t nframes, const uint64_t *sel, size_t nsel, const uint64_t *count,
+                     const DecodeOut &o, const CallerWs *cw, void *stream) {
+    if (!c) return -EINVAL;
+    if (nsel == 0 || nframes == 0) return 0;
+    size_t ncw;
+    if (int r = il_check(c, frames, frame_pitch, sym_stride, depth, len, nframes, ncw)) return r;
+    if (!sel) return -EINVAL;
+    if (int r = check_decode_out(c, nsel, o)) return r;
+    const IlSelect sl{sel, count, ncw};
+    return il_run(c, frames, frame_pitch, sym_stride, depth, len, nsel, &o, cw, stream, nullptr, &sl);
+}
+
+} // namespace
+
+size_t ezrs_select_workspace_bytes(size_t n) { return select_ws_bytes(n); }
+
+int ezrs_select_failed(const ezrs_codec *c, const int32_t *result, size_t n, uint64_t base, uint64_t *sel,
+                       size_t cap, uint64_t *count, void *stream) {
+    return select_failed(c, result, n, base, sel, cap, count, nullptr, stream);
+}
+
+int ezrs_select_failed_ws(const ezrs_codec *c, const int32_t *result, size_t n, uint64_t base, uint64_t *sel,
+                          size_t cap, uint64_t *count, void *ws, size_t ws_bytes, void *stream) {
+    const CallerWs cw{ws, ws_bytes};
+    return select_failed(c, result, n, base, sel, cap, count, &cw, stream);
+}
+
+size_t ezrs_decode_select_workspace_bytes(const ezrs_codec *c, unsigned len, size_t nsel) {
+    if (!c || len < 1 || len > c->dev.load || nsel == 0) return 0;
+    return il_ws_bytes(c, len, nsel);
+}
+
+int ezrs_decode_ptrs_select(const ezrs_codec *c, void *const *table, size_t table_pitch, unsigned len,
+                            size_t shard_len, size_t nstripes, const uint64_t *sel, size_t nsel,
+                            const uint64_t *count, const uint32_t *eras, size_t eras_stride, const uint32_t *neras,
+                            int32_t *result, uint32_t *positions, size_t pos_stride, void *corr,
+                            size_t corr_stride, void *stream) {
+    return decode_ptrs_select(c, table, table_pitch, len, shard_len, nstripes, sel, nsel, count,
+                              {eras, eras_stride, neras, result, positions, pos_stride, corr, corr_stride}, nullptr,
+                              stream);
+}
+
+int ezrs_decode_ptrs_select_ws(const ezrs_codec *c, void *const *table, size_t table_pitch, unsigned len,
+                               size_t shard_len, size_t nstripes, const uint64_t *sel, size_t nsel,
+                               const uint64_t *count, const uint32_t *eras, size_t eras_stride,
+                               const uint32_t *neras, int32_t *result, uint32_t *positions, size_t pos_stride,
+                               void *corr, size_t corr_stride, void *ws, size_t ws_bytes, void *stream) {
+    const CallerWs cw{ws, ws_bytes};
+    return decode_ptrs_select(c, table, table_pitch, len, shard_len, nstripes, sel, nsel, count,
+                              {eras, eras_stride, neras, result, positions, pos_stride, corr, corr_stride}, &cw,
+                              stream);
+}
+
+int ezrs_decode_interleaved_select(const ezrs_codec *c, void *frames, size_t frame_pitch, size_t sym_stride,
+                                   size_t depth, unsigned len, size_t nframes, const uint64_t *sel, size_t nsel,
+                                   const uint64_t *count, const uint32_t *eras, size_t eras_stride,
+                                   const uint32_t *neras, int32_t *result, uint32_t *positions, size_t pos_stride,
+                                   void *corr, size_t corr_stride, void *stream) {
+    return decode_il_select(c, frames, frame_pitch, sym_stride, depth, len, nframes, sel, nsel, count,
+                            {eras, eras_stride, neras, result, positions, pos_stride, corr, corr_stride}, nullptr,
+                            stream);
+}
+
+int ezrs_decode_interleaved_select_ws(const ezrs_codec *c, void *frames, size_t frame_pitch, size_t sym_stride,
+                                      size_t depth, unsigned len, size_t nframes, const uint64_t *sel,
+                                      size_t nsel, const uint64_t *count, const uint32_t *eras,
+                                      size_t eras_stride, const uint32_t *neras, int32_t *result,
+                                      uint32_t *positions, size_t pos_stride, void *corr, size_t corr_stride,
+                                      void *ws, size_t ws_bytes, void *stream) {
+    const CallerWs cw{ws, ws_bytes};
+    return decode_il_select(c, frames, frame_pitch, sym_stride, depth, len, nframes, sel, nsel, count,
+                            {eras, eras_stride, neras, result, positions, pos_stride, corr, corr_stride}, &cw,
+                            stream);
 }
 
 int ezrs_update_bitmatrix(unsigned symbol_bits, unsigned poly, unsigned fcr, unsigned prim, unsigned nroots,

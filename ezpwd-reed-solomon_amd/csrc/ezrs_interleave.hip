@@ -39,6 +39,13 @@
 // do not wait for a table load each; a tile that spans stripes reads its entries from the table,
 // one per symbol access.  The pointer fast path needs shard_len and every pointer to be multiples
 // of 4; tiles start at multiples of 256 codewords, so a quad of codewords never straddles stripes.
+// Selection (IlSel<B> over either policy; ezrs_decode_ptrs_select / ezrs_decode_interleaved_select):
+// staged row i is codeword sel[i], so a tile's 256 rows are 256 codewords anywhere in the batch.  A
+// thread reads its row's entry once (coalesced) and does its one division; off[] and row[] then mean
+// what they mean in the "tile spans stripes" path, and off[] = kSkip marks a skipped row, which the
+// gather stages as zeros and the scatter leaves out of flag[].  Neighbouring rows are not
+// neighbouring codewords, so there is no dword path and the lanes of a wave go along the symbols
+// (LS from len + NROOTS): in the pointer form they read consecutive table entries of one stripe.
 #include "ezrs_internal.hpp"
 
 namespace ezrs {
@@ -81,7 +88,11 @@ __device__ __forceinline__ size_t frame_off(const IlArgs &a, size_t k) {
 }
 
 template <class A>
-constexpr bool kPtrs = std::is_same_v<A, IlPtrArgs>;
+constexpr bool kPtrs = std::is_base_of_v<IlPtrArgs, A>;
+template <class A>
+constexpr bool kSel = false;
+template <class B>
+constexpr bool kSel<IlSel<B>> = true;
 
 // What a tile of the pointer policy keeps in LDS besides off[] (which holds j): the first table
 // entry of every codeword's stripe and, for a tile in one stripe, the buffers of the symbol chunk.
@@ -106,6 +117,30 @@ __device__ __forceinline__ void ptr_tile(const IlPtrArgs &a, size_t k, unsigned 
     else frame_of(a.depth, k + t, f, j);            // t >= nk: an entry that is never used
     off[t] = j;
     pt.row[t] = f * a.pitch;
+}
+
+constexpr size_t kSkip = ~(size_t)0;              // off[] of a selected row that is skipped
+
+// Selection: (stripe, element) or the frame offset of the codeword of row i of the call into off[]
+// (and row[]), for thread t; want: the row is needed at all.  False: not wanted, or skipped.
+template <class A>
+__device__ __forceinline__ bool sel_tile(const A &a, size_t i, bool want, unsigned t, size_t *off,
+                                         PtrTile<kPtrs<A>> &pt) {
+    typedef __attribute__((address_space(1))) const uint64_t Mem;   // global memory, as the table is
+    size_t k = 0, f = 0, j = 0;
+    bool use = want && (!a.count || i < *(Mem *)a.count);
+    if (use) {
+        k = ((Mem *)a.sel)[i];
+        use = k < a.ncw;
+    }
+    if (use) frame_of(a.depth, k, f, j);
+    if constexpr (kPtrs<A>) {
+        off[t] = use ? j : kSkip;
+        pt.row[t] = f * a.pitch;
+    } else {
+        off[t] = use ? f * a.frame_pitch + j : kSkip;
+    }
+    return use;
 }
 
 // Entry e of the pointer table, read as the global memory it is (see At).
@@ -151,7 +186,7 @@ struct At {
 // Frames -> rows.  lg = log2(LS).
 template <typename T, bool FAST, class A>
 __global__ void __launch_bounds__(256) k_il_gather(A a, unsigned lg) {
-    constexpr bool PTRS = kPtrs<A>;
+    constexpr bool PTRS = kPtrs<A>, SEL = kSel<A>;
     // 16 guard bytes on either side: a partial slot's aligned dword reads may start before row 0
     // and end after row 255 (those bytes are never stored)
     __shared__ __attribute__((aligned(16))) uint8_t lds[16 + kTile * kPitchB + 16];
@@ -164,14 +199,15 @@ __global__ void __launch_bounds__(256) k_il_gather(A a, unsigned lg) {
     const unsigned nk = a.n - kt0 < kTile ? (unsigned)(a.n - kt0) : kTile;
     bool one = false;
     size_t row0 = 0;
-    if constexpr (PTRS) ptr_tile(a, a.k0 + kt0, nk, t, off, pt, one, row0);
+    if constexpr (SEL) sel_tile(a, a.k0 + kt0 + t, t < nk, t, off, pt);
+    else if constexpr (PTRS) ptr_tile(a, a.k0 + kt0, nk, t, off, pt, one, row0);
     else off[t] = t < nk ? frame_off(a, a.k0 + kt0 + t) : 0;
     const T *frames = static_cast<const T *>(a.frames);
     uint8_t *rb = static_cast<uint8_t *>(a.rows);
     const unsigned ls = 1u << lg, si = t & (ls - 1), ki = t >> lg, kstep = 256u >> lg;
     for (unsigned sa = a.s0; sa < a.s1; sa += SC) {
         const unsigned ns = a.s1 - sa < SC ? a.s1 - sa : SC;
-        if constexpr (PTRS)                         // the last chunk's frame side is behind a barrier
+        if constexpr (PTRS && !SEL)                 // the last chunk's frame side is behind a barrier
             if (one && t < ns) pt.sym[t] = table_at(a, row0 + sa + t);
         __syncthreads();                            // off[] written; the tile's last chunk stored
         const auto frame_side = [&](auto at) {
@@ -193,13 +229,18 @@ __global__ void __launch_bounds__(256) k_il_gather(A a, unsigned lg) {
             } else {
                 T *lt = reinterpret_cast<T *>(tile);
                 for (unsigned kk = ki; kk < nk; kk += kstep) {
+                    if constexpr (SEL)
+                        if (off[kk] == kSkip) {     // a skipped row: the all-zero word, nothing read
+                            for (unsigned s = si; s < ns; s += ls) lt[kk * PT + s] = 0;
+                            continue;
+                        }
                     const auto p = at.cw(off[kk]);
 #pragma unroll 8
                     for (unsigned s = si; s < ns; s += ls) lt[kk * PT + s] = *at.sym(p, kk, s);
                 }
             }
         };
-        if (PTRS && one) frame_side(At<const T, A, PTRS>{a, frames, pt, sa});
+        if (PTRS && !SEL && one) frame_side(At<const T, A, PTRS && !SEL>{a, frames, pt, sa});
         else frame_side(At<const T, A, false>{a, frames, pt, sa});
         __syncthreads();
         // rows: the 16-byte aligned slots of every row's segment [g, g + nb)
@@ -239,7 +280,7 @@ __global__ void __launch_bounds__(256) k_il_gather(A a, unsigned lg) {
 // Rows -> frames, for every codeword of the tile (result == null) or those with a nonzero result.
 template <typename T, bool FAST, class A>
 __global__ void __launch_bounds__(256) k_il_scatter(A a, unsigned lg) {
-    constexpr bool PTRS = kPtrs<A>;
+    constexpr bool PTRS = kPtrs<A>, SEL = kSel<A>;
     __shared__ __attribute__((aligned(16))) uint8_t tile[kTile * kPitchB];
     __shared__ size_t off[kTile];
     __shared__ PtrTile<PTRS> pt;
@@ -248,13 +289,14 @@ __global__ void __launch_bounds__(256) k_il_scatter(A a, unsigned lg) {
     const unsigned t = threadIdx.x;
     const size_t kt0 = (size_t)blockIdx.x * kTile;
     const unsigned nk = a.n - kt0 < kTile ? (unsigned)(a.n - kt0) : kTile;
-    const bool mine = t < nk && (!a.result || a.result[kt0 + t] != 0);
+    bool mine = t < nk && (!a.result || a.result[kt0 + t] != 0);
+    if constexpr (SEL) mine = sel_tile(a, a.k0 + kt0 + t, mine, t, off, pt);   // and not skipped
     flag[t] = mine;
     if (!__syncthreads_or(mine)) return;            // a tile of clean codewords: nothing to write
     bool one = false;
     size_t row0 = 0;
-    if constexpr (PTRS) ptr_tile(a, a.k0 + kt0, nk, t, off, pt, one, row0);
-    else off[t] = mine ? frame_off(a, a.k0 + kt0 + t) : 0;
+    if constexpr (PTRS && !SEL) ptr_tile(a, a.k0 + kt0, nk, t, off, pt, one, row0);
+    else if constexpr (!SEL) off[t] = mine ? frame_off(a, a.k0 + kt0 + t) : 0;
     T *frames = static_cast<T *>(a.frames);
     const uint8_t *rb = static_cast<const uint8_t *>(a.rows);
     const unsigned ls = 1u << lg, si = t & (ls - 1), ki = t >> lg, kstep = 256u >> lg;
@@ -262,7 +304,7 @@ __global__ void __launch_bounds__(256) k_il_scatter(A a, unsigned lg) {
         const unsigned ns = a.s1 - sa < SC ? a.s1 - sa : SC;
         const unsigned nb = ns * (unsigned)sizeof(T);
         __syncthreads();
-        if constexpr (PTRS)                         // read after the next barrier
+        if constexpr (PTRS && !SEL)                 // read after the next barrier
             if (one && t < ns) pt.sym[t] = table_at(a, row0 + sa + t);
         // rows -> LDS: 16-byte LDS slots from aligned global dwords (reads may run up to 19 bytes
         // past the segment: inside the staging area, il_stage_bytes)
@@ -318,7 +360,7 @@ __global__ void __launch_bounds__(256) k_il_scatter(A a, unsigned lg) {
                 }
             }
         };
-        if (PTRS && one) frame_side(At<T, A, PTRS>{a, frames, pt, sa});
+        if (PTRS && !SEL && one) frame_side(At<T, A, PTRS && !SEL>{a, frames, pt, sa});
         else frame_side(At<T, A, false>{a, frames, pt, sa});
     }
 }
@@ -343,18 +385,27 @@ static unsigned lanes_log2(size_t depth, bool fast) {
     return lg;
 }
 
+// Selection: the lanes go along the symbols, as many as a row has (at most a wave).
+static unsigned sel_lanes_log2(size_t syms) {
+    unsigned lg = 0;
+    while (lg < 6 && ((size_t)1 << lg) < syms) ++lg;
+    return lg;
+}
+
 template <bool GATHER, class A>
 static hipError_t launch(const DevCodec &d, const A &a, bool fast, hipStream_t s) {
     if (!a.n || a.s0 >= a.s1) return hipSuccess;
     if (a.n > kIlMaxRows) return hipErrorInvalidValue;
-    const unsigned lg = lanes_log2(a.depth, fast);
+    const unsigned lg = kSel<A> ? sel_lanes_log2(a.row_pitch) : lanes_log2(a.depth, fast);
     const dim3 grid((unsigned)((a.n + kTile - 1) / kTile)), block(256);
     if (d.mm > 8) {
         if (GATHER) hipLaunchKernelGGL((k_il_gather<uint16_t, false, A>), grid, block, 0, s, a, lg);
         else hipLaunchKernelGGL((k_il_scatter<uint16_t, false, A>), grid, block, 0, s, a, lg);
-    } else if (fast) {
-        if (GATHER) hipLaunchKernelGGL((k_il_gather<uint8_t, true, A>), grid, block, 0, s, a, lg);
-        else hipLaunchKernelGGL((k_il_scatter<uint8_t, true, A>), grid, block, 0, s, a, lg);
+    } else if (!kSel<A> && fast) {
+        if constexpr (!kSel<A>) {
+            if (GATHER) hipLaunchKernelGGL((k_il_gather<uint8_t, true, A>), grid, block, 0, s, a, lg);
+            else hipLaunchKernelGGL((k_il_scatter<uint8_t, true, A>), grid, block, 0, s, a, lg);
+        }
     } else {
         if (GATHER) hipLaunchKernelGGL((k_il_gather<uint8_t, false, A>), grid, block, 0, s, a, lg);
         else hipLaunchKernelGGL((k_il_scatter<uint8_t, false, A>), grid, block, 0, s, a, lg);
@@ -389,6 +440,14 @@ hipError_t launch_il_gather(const DevCodec &d, const IlPtrArgs &a, size_t al, hi
 }
 hipError_t launch_il_scatter(const DevCodec &d, const IlPtrArgs &a, size_t al, hipStream_t s) {
     return il::launch<false>(d, a, il::fast_ok(d, a, al), s);
+}
+// Selection over the strided policy: the same arguments without the table.
+static IlSel<IlArgs> sel_strided(const IlSel<IlPtrArgs> &a) { return {{(const IlArgs &)a}, a.sel, a.count, a.ncw}; }
+hipError_t launch_il_gather(const DevCodec &d, const IlSel<IlPtrArgs> &a, bool ptrs, hipStream_t s) {
+    return ptrs ? il::launch<true>(d, a, false, s) : il::launch<true>(d, sel_strided(a), false, s);
+}
+hipError_t launch_il_scatter(const DevCodec &d, const IlSel<IlPtrArgs> &a, bool ptrs, hipStream_t s) {
+    return ptrs ? il::launch<false>(d, a, false, s) : il::launch<false>(d, sel_strided(a), false, s);
 }
 hipError_t launch_il_table(const PtrTable &tab, unsigned n, void **out, hipStream_t s) {
     hipLaunchKernelGGL(il::k_il_table, dim3(1), dim3(kPtrsMax), 0, s, tab, n, out);

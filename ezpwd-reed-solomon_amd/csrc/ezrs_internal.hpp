@@ -206,6 +206,30 @@ struct IlPtrArgs : IlArgs {
 };
 hipError_t launch_il_gather(const DevCodec &d, const IlPtrArgs &a, size_t al, hipStream_t s);
 hipError_t launch_il_scatter(const DevCodec &d, const IlPtrArgs &a, size_t al, hipStream_t s);
+// The selection policy of the same two kernels (ezrs_decode_ptrs_select /
+// ezrs_decode_interleaved_select), over either of the policies B above: staged row i of the call is
+// codeword sel[i] of the ncw = nframes * depth codewords that B addresses, so k0 and n count rows of
+// `sel` (and of `result`), not codewords of the batch.  A row is skipped when i >= count[0] (count
+// non-null) or sel[i] >= ncw: the gather stages it as zeros and reads nothing for it, the scatter
+// never writes it.  sel and count are DEVICE memory, read while the kernels run.  Element path only:
+// neighbouring rows are not neighbouring codewords.
+template <class B>
+struct IlSel : B {
+    const uint64_t *sel;
+    const uint64_t *count;
+    size_t ncw;
+};
+hipError_t launch_il_gather(const DevCodec &d, const IlSel<IlPtrArgs> &a, bool ptrs, hipStream_t s);
+hipError_t launch_il_scatter(const DevCodec &d, const IlSel<IlPtrArgs> &a, bool ptrs, hipStream_t s);
+
+// Order-preserving compaction of the failed codewords of a result array (ezrs_select.hip;
+// ezrs_select_failed): sel[0 .. min(total, cap) - 1] = base + k for the k < n with result[k] < 0,
+// ascending, the rest of sel[0 .. cap - 1] = EZRS_SEL_NONE, *count = total.  Three kernels on the
+// stream (counts per chunk of kSelChunk results, their scan, the write); ws: select_ws_bytes(n).
+constexpr size_t kSelChunk = 4096;
+inline size_t select_ws_bytes(size_t n) { return (n / kSelChunk + (n % kSelChunk != 0)) * sizeof(uint64_t); }
+hipError_t launch_select_failed(const int32_t *result, size_t n, uint64_t base, uint64_t *sel, size_t cap,
+                                uint64_t *count, void *ws, hipStream_t s);
 
 // Shared-erasure reconstruction of interleaved frames (ezrs_recon.hip; ezrs_recon_create /
 // ezrs_reconstruct_interleaved): one constant GF matrix per loss pattern, applied to the survivors

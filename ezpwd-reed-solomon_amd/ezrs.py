@@ -124,6 +124,21 @@ def lib():
                                              _sz, _vp, _sz, _vp]
         L.ezrs_decode_ptrs_batch_ws.argtypes = [_vp, _vp, _sz, _u, _sz, _sz, _u, _vp, _sz, _vp, _vp,
                                                 _vp, _sz, _vp, _sz, _vp, _sz, _vp]
+        L.ezrs_select_workspace_bytes.restype = _sz
+        L.ezrs_select_workspace_bytes.argtypes = [_sz]
+        L.ezrs_select_failed.argtypes = [_vp, _vp, _sz, C.c_uint64, _vp, _sz, _vp, _vp]
+        L.ezrs_select_failed_ws.argtypes = [_vp, _vp, _sz, C.c_uint64, _vp, _sz, _vp, _vp, _sz, _vp]
+        L.ezrs_decode_select_workspace_bytes.restype = _sz
+        L.ezrs_decode_select_workspace_bytes.argtypes = [_vp, _u, _sz]
+        L.ezrs_decode_ptrs_select.argtypes = [_vp, _vp, _sz, _u, _sz, _sz, _vp, _sz, _vp, _vp, _sz, _vp,
+                                              _vp, _vp, _sz, _vp, _sz, _vp]
+        L.ezrs_decode_ptrs_select_ws.argtypes = [_vp, _vp, _sz, _u, _sz, _sz, _vp, _sz, _vp, _vp, _sz, _vp,
+                                                 _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp]
+        L.ezrs_decode_interleaved_select.argtypes = [_vp, _vp, _sz, _sz, _sz, _u, _sz, _vp, _sz, _vp, _vp,
+                                                     _sz, _vp, _vp, _vp, _sz, _vp, _sz, _vp]
+        L.ezrs_decode_interleaved_select_ws.argtypes = [_vp, _vp, _sz, _sz, _sz, _u, _sz, _vp, _sz, _vp,
+                                                        _vp, _sz, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz,
+                                                        _vp]
         L.ezrs_kernel_path.argtypes = [_vp]
         L.ezrs_set_launch_rows.argtypes = [_vp, _sz]
         L.ezrs_set_semantics.argtypes = [_vp, _i]
@@ -498,6 +513,100 @@ class Codec:
                                             *out, _stream_ptr(stream)), "ezrs_decode_ptrs_batch")
         return result
 
+    # -- selection: list the failed codewords of a verify on the device, decode only those --------
+    def _sel_list(self, t, what, n=None):
+        """Validate an int64 1-D contiguous device tensor (of at least n entries); None passes."""
+        import torch
+        if t is None:
+            return
+        _dev_rows(t, what, self.device, 8, ndim=1)
+        if t.dtype != torch.int64:
+            raise EzrsError(f"{what}: expected int64 entries, got {t.dtype}")
+        if t.shape[0] > 1 and t.stride(0) != 1:
+            raise EzrsError(f"{what}: expected a contiguous tensor")
+        if n is not None and t.shape[0] < n:
+            raise EzrsError(f"{what}: {t.shape[0]} entries, the call needs {n}")
+
+    def _sel_rows(self, sel, count, **outs):
+        """The checks the two selected decodes share; returns nsel.  The outputs are compact: a row
+        per entry of sel."""
+        self._sel_list(sel, "sel", 0)
+        self._sel_list(count, "count", 1)
+        if sel is None:
+            raise EzrsError("sel: None")
+        for what, t in outs.items():
+            if t is not None and getattr(t, "shape", None) is not None and t.shape[0] < sel.shape[0]:
+                raise EzrsError(f"{what}: {t.shape[0]} rows, sel has {sel.shape[0]} entries")
+        return sel.shape[0]
+
+    def select_workspace_bytes(self, n):
+        return int(lib().ezrs_select_workspace_bytes(n))
+
+    def select_failed(self, result, cap=None, base=0, sel=None, count=None, stream=None):
+        """ezrs_select_failed: result is an int32 1-D contiguous device tensor (a verify's or a
+        decode's); returns (sel, count), int64 device tensors of cap entries (default: one per
+        result) and of one: sel[:min(count, cap)] = base + k for every k with result[k] < 0,
+        ascending, the rest of sel ``SEL_NONE``, count the number of such k (it may exceed cap).
+        Nothing is read on the host: both feed ``decode_ptrs_select`` / ``decode_interleaved_select``
+        on the same stream as they are."""
+        import torch
+        _dev_rows(result, "result", self.device, 4, ndim=1)
+        if result.dtype != torch.int32:
+            raise EzrsError(f"result: expected int32 entries, got {result.dtype}")
+        n = result.shape[0]
+        if n > 1 and result.stride(0) != 1:
+            raise EzrsError("result: expected a contiguous tensor")
+        cap, base = (n if cap is None else int(cap)), int(base)
+        if cap < 0 or base < 0:
+            raise EzrsError("cap, base: negative")
+        if sel is None:
+            sel = torch.empty(cap, dtype=torch.int64, device=result.device)
+        if count is None:
+            count = torch.empty(1, dtype=torch.int64, device=result.device)
+        self._sel_list(sel, "sel", cap)
+        self._sel_list(count, "count", 1)
+        # an empty tensor may have no address: with cap == 0 nothing is written through sel
+        _check(lib().ezrs_select_failed(self._h, _tp(result), n, base, _tp(sel if cap else count), cap,
+                                        _tp(count), _stream_ptr(stream)), "ezrs_select_failed")
+        return sel, count
+
+    def decode_select_workspace_bytes(self, length, nsel):
+        return int(lib().ezrs_decode_select_workspace_bytes(self._h, length, nsel))
+
+    def decode_ptrs_select(self, table, length, shard_len, sel, count=None, eras=None, neras=None,
+                           result=None, positions=None, corr=None, stream=None):
+        """ezrs_decode_ptrs_select: ``decode_ptrs_batch`` of only the codewords sel names.  table,
+        length and shard_len as there (no align: symbols move one element at a time); sel: an int64
+        device tensor, row i of the call decodes codeword sel[i] = s * shard_len + j; count: None, or
+        an int64 device tensor whose first entry bounds the rows used.  A row past count[0], or whose
+        entry is not a codeword of the table (``SEL_NONE``), is skipped: nothing of it is read or
+        written and its outputs are those of an all-zero codeword.  eras, neras, result, positions
+        and corr have one row per entry of sel.  sel, count and the table are read while the kernels
+        run.  Returns the int32 result tensor [len(sel)]."""
+        nstripes, pitch = _ptr_table(table, "table", length + self.nroots, self.device)
+        shard_len = int(shard_len)
+        if shard_len < 0:
+            raise EzrsError("shard_len: negative")
+        nsel = self._sel_rows(sel, count, eras=eras, neras=neras, result=result, positions=positions, corr=corr)
+        result, out = self._decode_out(nsel, eras, neras, result, positions, corr, like=table)
+        _check(lib().ezrs_decode_ptrs_select(self._h, _tp(table), pitch, length, shard_len, nstripes, _tp(sel),
+                                             nsel, _tp(count), *out, _stream_ptr(stream)),
+               "ezrs_decode_ptrs_select")
+        return result
+
+    def decode_interleaved_select(self, frames, sel, count=None, eras=None, neras=None, result=None,
+                                  positions=None, corr=None, stream=None):
+        """ezrs_decode_interleaved_select: ``decode_interleaved`` of only the codewords sel names,
+        sel[i] = f * depth + j; sel, count and the outputs as in ``decode_ptrs_select``.  Returns the
+        int32 result tensor [len(sel)]."""
+        fp, ss, depth, length, nframes = self._frames(frames)
+        nsel = self._sel_rows(sel, count, eras=eras, neras=neras, result=result, positions=positions, corr=corr)
+        result, out = self._decode_out(nsel, eras, neras, result, positions, corr, like=frames)
+        _check(lib().ezrs_decode_interleaved_select(self._h, _tp(frames), fp, ss, depth, length, nframes,
+                                                    _tp(sel), nsel, _tp(count), *out, _stream_ptr(stream)),
+               "ezrs_decode_interleaved_select")
+        return result
+
     def recon_plan(self, length, lost):
         """Reconstruction plan for codewords of `length` data symbols whose symbols at the
         positions `lost` (relative to the first data symbol, parity at length..) are gone in
@@ -684,6 +793,7 @@ class Recon(_Plan):
 
 
 PLAN_SKIP = 0xFFFFFFFF                             # EZRS_PLAN_SKIP: in plan_of, leave this stripe alone
+SEL_NONE = -1                                      # EZRS_SEL_NONE as int64: in sel, skip this row
 
 
 class ReconSet(_Plan):

@@ -528,6 +528,96 @@ int ezrs_decode_ptrs_batch_ws(const ezrs_codec *codec, void *const *table, size_
                               int32_t *result, uint32_t *positions, size_t pos_stride, void *corr,
                               size_t corr_stride, void *ws, size_t ws_bytes, void *stream);
 
+/* Selection (device-resident): the end of a scrub.  A verify (ezrs_reconstruct_ptrs_batch or
+ * ezrs_reconstruct_interleaved under an nlost == 0 plan) marks the codewords whose check failed with
+ * result[k] == -1; the decodes above would gather and decode every codeword of every stripe they
+ * name.  These calls list the failed codewords on the device and decode only those, with no host
+ * read in between: verify, ezrs_select_failed and a *_select decode can sit in one stream or one
+ * captured graph.
+ *   ezrs_select_failed       everything is DEVICE memory on the codec's device.  sel[0 .. min(total,
+ *            cap) - 1] receives base + k for every k < n with result[k] < 0, in ascending k (the
+ *            order is deterministic; neighbouring k land in neighbouring rows of the decode, which is
+ *            what gives its gather any coalescing); sel[min(total, cap) .. cap - 1] is set to
+ *            EZRS_SEL_NONE; count[0] receives total, which may exceed cap: the caller sees the
+ *            overflow when it reads count, the decode clamps.  `codec` supplies the device and, in
+ *            the form without _ws, the stream's workspace; nothing else of it is used.  base lets a
+ *            caller verify a batch in pieces and number the codewords over the whole.  Three
+ *            kernels on `stream` (counts per chunk of results, their scan, the write): no workgroup
+ *            ever waits for another one.  Asynchronous; the _ws form takes a caller-owned workspace
+ *            of exactly ezrs_select_workspace_bytes(n) bytes or more, allocates nothing and
+ *            synchronises nothing.  n == 0 or cap == 0 still writes count[0] (0 for n == 0) and
+ *            returns 0.  -EINVAL: a null codec, sel or count; a null result with n != 0; base + n
+ *            overflowing 64 bits; a workspace that is too small.
+ *   ezrs_decode_ptrs_select / ezrs_decode_interleaved_select   the geometry (table .. nstripes,
+ *            frames .. nframes) is that of ezrs_decode_ptrs_batch / ezrs_decode_interleaved and names
+ *            the same codewords, k = s*shard_len + j or f*depth + j.  Row i (0 <= i < nsel) of the
+ *            call is codeword k = sel[i]: result[i], neras[i] and the rows i of eras, positions and
+ *            corr belong to it, so these arrays are compact, sized by nsel and not by the batch, and
+ *            follow the stride rules of ezrs_decode over nsel codewords.  Per selected codeword the
+ *            bytes left in the shards or frames, the result, the positions and the corrections equal
+ *            what the full call produces for codeword k under the same erasures, under both
+ *            semantics of the codec (a -1 row carries the reference's partial corrections).  No
+ *            symbol of a codeword that is not selected is read for its own sake, and no byte outside
+ *            the selected codewords' symbols is ever written: not a codeword that was left out, not
+ *            a gap of sym_stride > depth, not a guard byte.
+ *            count: nullable DEVICE pointer; the call uses the rows i < min(count[0], nsel).  sel
+ *            and count are read by the kernels WHILE THEY RUN, never by the host, so both may be
+ *            the outputs of an ezrs_select_failed queued before on the same stream.
+ *            A row is skipped when it is past count[0] or its entry is >= nstripes*shard_len
+ *            (nframes*depth); EZRS_SEL_NONE is the canonical skip value.  For a skipped row no table
+ *            entry and no symbol is read and nothing is scattered; it is staged as the all-zero word,
+ *            so result[i] / positions / corr are what ezrs_decode gives for an all-zero codeword of
+ *            length len under row i's erasures (0 when there are none).  That keeps the launch shape
+ *            a host constant (capturable); a caller who knows the count on the host passes it as
+ *            nsel with count == NULL and stages nothing spare.
+ *            Entries must be distinct (NOT CHECKED: a duplicate has two rows writing the same
+ *            symbols); any order is valid.  Pointers need only the datum's alignment: there is no
+ *            `align`, because a row's neighbours are not its codeword's neighbours and symbols move
+ *            one element at a time, one memory sector per symbol.  The table is read while the
+ *            kernels run; EZRS_PTRS_MAX does not apply; what ezrs_decode_ptrs_batch lists as not
+ *            checked holds here for the stripes of the selected codewords.
+ *            Checked on the host: what the corresponding full call checks (without align), over nsel
+ *            rows for the outputs, and a null sel.  nsel == 0 returns 0 and touches nothing (after
+ *            the null-codec check), and so do nstripes == 0, shard_len == 0 and nframes == 0.
+ *            Asynchronous.  Rows are staged a bounded number per pass as in the full calls, over
+ *            nsel; the forms without _ws use the calling stream's workspace, the _ws forms a
+ *            caller-owned one of >= ezrs_decode_select_workspace_bytes(codec, len, nsel) bytes (what
+ *            a call of either form uses; 0 for invalid arguments): they allocate nothing and
+ *            synchronise nothing. */
+#define EZRS_SEL_NONE UINT64_MAX   /* in sel: no codeword, skip this row */
+size_t ezrs_select_workspace_bytes(size_t n);
+int ezrs_select_failed(const ezrs_codec *codec, const int32_t *result, size_t n, uint64_t base,
+                       uint64_t *sel, size_t cap, uint64_t *count, void *stream);
+int ezrs_select_failed_ws(const ezrs_codec *codec, const int32_t *result, size_t n, uint64_t base,
+                          uint64_t *sel, size_t cap, uint64_t *count, void *ws, size_t ws_bytes,
+                          void *stream);
+size_t ezrs_decode_select_workspace_bytes(const ezrs_codec *codec, unsigned len, size_t nsel);
+int ezrs_decode_ptrs_select(const ezrs_codec *codec, void *const *table, size_t table_pitch,
+                            unsigned len, size_t shard_len, size_t nstripes, const uint64_t *sel,
+                            size_t nsel, const uint64_t *count, const uint32_t *eras,
+                            size_t eras_stride, const uint32_t *neras, int32_t *result,
+                            uint32_t *positions, size_t pos_stride, void *corr, size_t corr_stride,
+                            void *stream);
+int ezrs_decode_ptrs_select_ws(const ezrs_codec *codec, void *const *table, size_t table_pitch,
+                               unsigned len, size_t shard_len, size_t nstripes, const uint64_t *sel,
+                               size_t nsel, const uint64_t *count, const uint32_t *eras,
+                               size_t eras_stride, const uint32_t *neras, int32_t *result,
+                               uint32_t *positions, size_t pos_stride, void *corr,
+                               size_t corr_stride, void *ws, size_t ws_bytes, void *stream);
+int ezrs_decode_interleaved_select(const ezrs_codec *codec, void *frames, size_t frame_pitch,
+                                   size_t sym_stride, size_t depth, unsigned len, size_t nframes,
+                                   const uint64_t *sel, size_t nsel, const uint64_t *count,
+                                   const uint32_t *eras, size_t eras_stride, const uint32_t *neras,
+                                   int32_t *result, uint32_t *positions, size_t pos_stride,
+                                   void *corr, size_t corr_stride, void *stream);
+int ezrs_decode_interleaved_select_ws(const ezrs_codec *codec, void *frames, size_t frame_pitch,
+                                      size_t sym_stride, size_t depth, unsigned len, size_t nframes,
+                                      const uint64_t *sel, size_t nsel, const uint64_t *count,
+                                      const uint32_t *eras, size_t eras_stride,
+                                      const uint32_t *neras, int32_t *result, uint32_t *positions,
+                                      size_t pos_stride, void *corr, size_t corr_stride, void *ws,
+                                      size_t ws_bytes, void *stream);
+
 /* Host-memory forms: the same contracts with HOST pointers.  The batch is streamed through the
  * device in chunks of `chunk` codewords (0 = library default) over two HIP streams with
  * asynchronous copies; pinned host memory (ezrs_host_alloc) gets full PCIe overlap.  Blocking:

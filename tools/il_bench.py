@@ -15,7 +15,12 @@ GB/s counts the frames' bytes once (ncw * 255).
     python tools/il_bench.py --ptrs [--out profiles/il/il_ptrs_bench.json]
 
 The pointer forms of the staged decode (ezrs_decode_ptrs / ezrs_decode_ptrs_batch) against
-ezrs_decode_interleaved on the same symbols, same method: see ptrs_main."""
+ezrs_decode_interleaved on the same symbols, same method: see ptrs_main.
+
+    python tools/il_bench.py --select [--out profiles/il/il_select_bench.json]
+
+The scrub with selection (verify, ezrs_select_failed, ezrs_decode_ptrs_select) against
+ezrs_decode_ptrs_batch over all stripes, same method: see select_main."""
 import argparse
 import json
 import os
@@ -140,14 +145,120 @@ def ptrs_main(out_path):
     print("wrote", out_path)
 
 
+# --select: the fast-path shapes of PTRS_SHAPES and the corrupted fractions
+SELECT_SHAPES = [s for s in PTRS_SHAPES if s[5] == 16]
+SELECT_FRACTIONS = [1e-2, 1e-4]
+CROSSOVER_SHAPE = "RS(255,251) 10+4 1024 x 64Ki a16"
+
+
+class SelectShape:
+    """One shape of --select: the stripes in buffers of their own, the table, and the two scrubs."""
+
+    def __init__(self, name, nk, L, F, D):
+        self.name, self.L, self.F, self.D = name, L, F, D
+        self.c = c = ezrs.Codec.rs(*nk)
+        self.S, self.ncw = S, ncw = L + c.nroots, F * D
+        self.g = g = torch.Generator(device="cuda").manual_seed(2)
+        self.fr = fr = torch.randint(0, 256, (F, S, D), generator=g, device="cuda", dtype=torch.int32).to(torch.uint8)
+        c.encode_interleaved(fr)
+        self.pitch = pitch = D + 16
+        self.arena = arena = torch.zeros((F, S, pitch), dtype=torch.uint8, device="cuda")
+        arena[:, :, :D] = fr
+        self.table = (arena.data_ptr() + torch.arange(F * S, dtype=torch.int64, device="cuda") * pitch).view(F, S)
+        self.plan = c.recon_plan(L, [])                  # nlost = 0: the verify
+        self.ver = torch.empty(ncw, dtype=torch.int32, device="cuda")
+        self.res_full = torch.empty(ncw, dtype=torch.int32, device="cuda")
+        self.count = torch.empty(1, dtype=torch.int64, device="cuda")
+
+    def measure(self, fraction):
+        """One symbol wrong in `fraction` of the codewords: both arms time [put the corruption back,
+        scrub]; returns the record."""
+        c, L, F, D, S, ncw, g = self.c, self.L, self.F, self.D, self.S, self.ncw, self.g
+        nbad = min(ncw, max(1, int(round(ncw * fraction))))
+        kk = torch.randperm(ncw, generator=g, device="cuda")[:nbad]
+        pp = torch.randint(0, S, (nbad,), generator=g, device="cuda")
+        ix = ((kk // D) * S + pp) * self.pitch + kk % D
+        flat = self.arena.view(-1)
+        wrong = flat[ix] ^ 0x5A
+        cap = 2 * nbad
+        sel = torch.empty(cap, dtype=torch.int64, device="cuda")
+        res_sel = torch.empty(cap, dtype=torch.int32, device="cuda")
+        table, ver, count, res_full, plan = self.table, self.ver, self.count, self.res_full, self.plan
+
+        def select():
+            flat[ix] = wrong
+            plan.reconstruct_ptrs_batch(table, D, align=16, result=ver)
+            c.select_failed(ver, cap=cap, sel=sel, count=count)
+            c.decode_ptrs_select(table, L, D, sel, count=count, result=res_sel)
+
+        def full():
+            flat[ix] = wrong
+            c.decode_ptrs_batch(table, L, D, align=16, result=res_full)
+
+        fg = figure({"select": select, "full": full})
+        torch.cuda.synchronize()
+        assert int(count[0]) == nbad == int(res_full.sum()) and bool((res_sel[:nbad] == 1).all())
+        assert bool((res_sel[nbad:] == 0).all()) and torch.equal(sel[:nbad], kk.sort().values)
+        assert torch.equal(self.arena[:, :, :D], self.fr)
+        ts, tf = fg["select"]["median_s"], fg["full"]["median_s"]
+        return {"shape": self.name, "len": L, "nstripes": F, "shard_len": D, "fraction": fraction,
+                "corrupted_codewords": nbad, "cap": cap,
+                "workspace_bytes_select": c.decode_select_workspace_bytes(L, cap) + c.select_workspace_bytes(ncw),
+                "workspace_bytes_full": c.decode_ptrs_workspace_bytes(L, D, F),
+                "t_select_ms": ts * 1e3, "t_full_ms": tf * 1e3, "ratio": ts / tf,
+                "spread_select": fg["select"]["spread"], "spread_full": fg["full"]["spread"]}
+
+
+def select_main(out_path):
+    """The scrub with selection against the full decode, on the fast-path shapes of --ptrs, one
+    symbol corrupted in 1 % and in 0.01 % of the codewords.
+      select  verify (reconstruct_ptrs_batch under an nlost = 0 plan, with result) + select_failed +
+              decode_ptrs_select with the device count, cap = 2 x the corrupted codewords
+      full    decode_ptrs_batch over all stripes (unchanged code)
+    Then the corrupted fraction at which both cost the same on the 64 KiB shape, by bisection over
+    the fraction (geometric midpoints) to within a factor of 2."""
+    out = {"reps": REPS, "device": torch.cuda.get_device_name(0), "results": [], "crossover": None}
+    for name, nk, L, F, D, _, _ in SELECT_SHAPES:
+        sh = SelectShape(name, nk, L, F, D)
+        for fraction in SELECT_FRACTIONS:
+            rec = sh.measure(fraction)
+            out["results"].append(rec)
+            print(json.dumps(rec), flush=True)
+        if name == CROSSOVER_SHAPE:
+            lo, hi, steps = 1e-4, 0.5, []               # select wins at lo, loses at hi?
+            ends = {f: sh.measure(f) for f in (lo, hi)}
+            steps += list(ends.values())
+            if ends[lo]["ratio"] >= 1 or ends[hi]["ratio"] < 1:
+                verdict = "below 1e-4" if ends[lo]["ratio"] >= 1 else "above 0.5"
+            else:
+                while hi / lo > 2:
+                    mid = (lo * hi) ** 0.5
+                    rec = sh.measure(mid)
+                    steps.append(rec)
+                    lo, hi = (mid, hi) if rec["ratio"] < 1 else (lo, mid)
+                verdict = "between"
+            out["crossover"] = {"shape": name, "verdict": verdict, "fraction_lo": lo, "fraction_hi": hi,
+                                "steps": steps}
+            print(json.dumps(out["crossover"]), flush=True)
+        del sh
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    with open(out_path, "w") as fh:
+        json.dump(out, fh, indent=1)
+    print("wrote", out_path)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ncw", type=int, default=1 << 20)
+    ap.add_argument("--select", action="store_true",
+                    help="the scrub with selection (verify, select_failed, decode_ptrs_select) against the full decode")
     ap.add_argument("--ptrs", action="store_true",
                     help="the pointer forms of the staged decode against the strided form")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     torch.cuda.set_device(0)
+    if args.select:
+        return select_main(args.out or os.path.join(ROOT, "profiles", "il", "il_select_bench.json"))
     if args.ptrs:
         return ptrs_main(args.out or os.path.join(ROOT, "profiles", "il", "il_ptrs_bench.json"))
     args.out = args.out or os.path.join(ROOT, "profiles", "il", "il_bench.json")
