@@ -5,6 +5,7 @@
 // points validate arguments the way the reference's encode<INP>/decode<INP> do
 // (rs_base:868-904, 1170-1242) and dispatch to the fastest kernel that is bit-exact for the codec:
 // the bit-sliced GF(2^8) kernels where they apply, the generic per-codeword kernels otherwise.
+#include <algorithm>
 #include <atomic>
 #include <cerrno>
 #include <cstdlib>
@@ -15,6 +16,7 @@
 #include <string>
 #include <thread>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 #include "../../include/ezrs.h"
@@ -74,15 +76,18 @@ struct ezrs_update : FramePlan {
     std::vector<uint32_t> chg;          // host copy of the changed positions (the pointer form)
 };
 
-// A set of reconstruction plans of one codec geometry in one device allocation (ReconMixedArgs):
-// copies of the plans' tables behind a directory.  Const after ezrs_recon_set_create; it keeps
-// nothing of the plans it was made from.
-struct ezrs_recon_set {
+// A set of plans of one kind and one codec geometry in one device allocation (ReconMixedArgs,
+// UpdateMixedArgs): copies of the plans' tables behind a directory.  Const after its *_set_create;
+// it keeps nothing of the plans it was made from.
+struct PlanSet {
     int device = 0;
     unsigned mm = 0, nroots = 0, len = 0;
-    unsigned nplans = 0, max_nlost = 0;
+    unsigned nplans = 0;
+    unsigned most = 0;                  // the largest nlost (reconstruction), nchanged (update) of the plans
     uint32_t *d_set = nullptr;
 };
+struct ezrs_recon_set : PlanSet {};
+struct ezrs_update_set : PlanSet {};
 
 namespace {
 
@@ -97,6 +102,90 @@ unsigned std_poly(unsigned mm) {
     static const unsigned p[17] = {0, 0, 0x7, 0xb, 0x13, 0x25, 0x43, 0x89, 0x11d, 0x211, 0x409,
                                    0x805, 0x1053, 0x201b, 0x4443, 0x8003, 0x1100b};
     return mm <= 16 ? p[mm] : 0;
+}
+
+template <class S>
+int destroy_set(S *s) {
+    if (!s) return 0;
+    DeviceGuard g(s->device);
+    if (s->d_set) (void)hipFree(s->d_set);
+    delete s;
+    return 0;
+}
+
+// What ezrs_recon_set_create and ezrs_update_set_create share: S the set, P the plan (a FramePlan),
+// kind: the set's name in the error texts; counts(plan): the survivors and the lost positions of the
+// plan's recon_table image, i.e. (nsurv, nlost) or (nchanged, NROOTS); most_lost: PlanSet::most is
+// the largest of the second of them, else of the first.
+template <class S, class P, class F>
+int create_set(S **out, const P *const *plans, unsigned nplans, const char *kind, F &&counts, bool most_lost) {
+    if (!out) return -EINVAL;
+    *out = nullptr;
+    auto bad = [kind](const char *what) {
+        g_last_error = std::string(kind) + ": " + what;
+        return -EINVAL;
+    };
+    if (!plans) return bad("null plans");
+    if (!nplans) return bad("no plans");
+    for (unsigned i = 0; i < nplans; ++i)
+        if (!plans[i]) return bad("a NULL plan");
+    const FramePlan *const p0 = plans[0];
+    for (unsigned i = 1; i < nplans; ++i) {
+        const FramePlan *const p = plans[i];
+        if (p->mm != p0->mm || p->nroots != p0->nroots || p->len != p0->len || p->device != p0->device)
+            return bad("plans that differ in symbol bits, NROOTS, len or device");
+    }
+    // directory | images, each at a multiple of kReconSetAlign dwords
+    auto up = [](size_t w) { return (w + kReconSetAlign - 1) / kReconSetAlign * kReconSetAlign; };
+    const size_t cap = kReconMaxTable / sizeof(uint32_t), ent = sizeof(ReconSetEntry) / sizeof(uint32_t);
+    size_t words = nplans <= cap / ent ? up(nplans * ent) : cap + 1;
+    std::vector<ReconSetEntry> dir;
+    std::vector<size_t> image;                      // dwords of plan i's table
+    unsigned most = 0;
+    try {
+        for (unsigned i = 0; i < nplans && words <= cap; ++i) {
+            const std::pair<unsigned, unsigned> c = counts(*plans[i]);
+            const unsigned nsurv = c.first, nlost = c.second;
+            dir.push_back({(uint32_t)words, nsurv, nlost,
+                           (uint32_t)(words + recon_coef_words(p0->mm, p0->nroots, nsurv))});
+            image.push_back(recon_table_words(p0->mm, p0->nroots, nsurv, nlost));
+            words += up(image.back());
+            most = std::max(most, most_lost ? nlost : nsurv);
+        }
+    } catch (const std::bad_alloc &) {
+        return -ENOMEM;
+    }
+    if (words > cap) {
+        g_last_error = std::string(kind) + ": device tables above 64 MiB together";
+        return -ENOTSUP;
+    }
+    S *s = new (std::nothrow) S;
+    if (!s) return -ENOMEM;
+    s->device = p0->device;
+    s->mm = p0->mm;
+    s->nroots = p0->nroots;
+    s->len = p0->len;
+    s->nplans = nplans;
+    s->most = most;
+    DeviceGuard g(s->device);
+    hipError_t e;
+    if ((e = hipMalloc(&s->d_set, words * sizeof(uint32_t))) != hipSuccess) {
+        delete s;
+        return hip_fail(e, ("hipMalloc(" + std::string(kind) + ")").c_str());
+    }
+    e = hipMemset(s->d_set, 0, words * sizeof(uint32_t));
+    if (e == hipSuccess)
+        e = hipMemcpy(s->d_set, dir.data(), dir.size() * sizeof(ReconSetEntry), hipMemcpyHostToDevice);
+    for (unsigned i = 0; i < nplans && e == hipSuccess; ++i)
+        e = hipMemcpy(s->d_set + dir[i].off, plans[i]->d_tab, image[i] * sizeof(uint32_t),
+                      hipMemcpyDeviceToDevice);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);   // the plans may be destroyed at once
+    if (e != hipSuccess) {
+        destroy_set(s);
+        return hip_fail(e, ("copy of the plans' tables (" + std::string(kind) + ")").c_str());
+    }
+    *out = s;
+    return 0;
 }
 
 } // namespace
@@ -1037,83 +1126,14 @@ int ezrs_update_ptrs_batch(const ezrs_update *p, void *const *table, size_t tabl
     return 0;
 }
 
-// ---- mixed batched reconstruction: many stripes, a plan per stripe ---------------------------------
+// ---- mixed batched forms: many stripes, a plan per stripe (create_set, destroy_set: above) ----------
 int ezrs_recon_set_create(ezrs_recon_set **out, const ezrs_recon *const *plans, unsigned nplans) {
-    if (!out) return -EINVAL;
-    *out = nullptr;
-    auto bad = [](const char *what) {
-        g_last_error = std::string("reconstruction set: ") + what;
-        return -EINVAL;
-    };
-    if (!plans) return bad("null plans");
-    if (!nplans) return bad("no plans");
-    for (unsigned i = 0; i < nplans; ++i)
-        if (!plans[i]) return bad("a NULL plan");
-    const ezrs_recon *const p0 = plans[0];
-    for (unsigned i = 1; i < nplans; ++i)
-        if (plans[i]->mm != p0->mm || plans[i]->nroots != p0->nroots || plans[i]->len != p0->len ||
-            plans[i]->device != p0->device)
-            return bad("plans that differ in symbol bits, NROOTS, len or device");
-    // directory | images, each at a multiple of kReconSetAlign dwords
-    auto up = [](size_t w) { return (w + kReconSetAlign - 1) / kReconSetAlign * kReconSetAlign; };
-    const size_t cap = kReconMaxTable / sizeof(uint32_t), ent = sizeof(ReconSetEntry) / sizeof(uint32_t);
-    size_t words = nplans <= cap / ent ? up(nplans * ent) : cap + 1;
-    std::vector<ReconSetEntry> dir;
-    unsigned max_nlost = 0;
-    try {
-        for (unsigned i = 0; i < nplans && words <= cap; ++i) {
-            const ezrs_recon *p = plans[i];
-            dir.push_back({(uint32_t)words, p->nsurv, p->nlost,
-                           (uint32_t)(words + recon_coef_words(p->mm, p->nroots, p->nsurv))});
-            words += up(recon_table_words(p->mm, p->nroots, p->nsurv, p->nlost));
-            max_nlost = std::max(max_nlost, p->nlost);
-        }
-    } catch (const std::bad_alloc &) {
-        return -ENOMEM;
-    }
-    if (words > cap) {
-        g_last_error = "reconstruction set: device tables above 64 MiB together";
-        return -ENOTSUP;
-    }
-    ezrs_recon_set *s = new (std::nothrow) ezrs_recon_set;
-    if (!s) return -ENOMEM;
-    s->device = p0->device;
-    s->mm = p0->mm;
-    s->nroots = p0->nroots;
-    s->len = p0->len;
-    s->nplans = nplans;
-    s->max_nlost = max_nlost;
-    DeviceGuard g(s->device);
-    hipError_t e;
-    if ((e = hipMalloc(&s->d_set, words * sizeof(uint32_t))) != hipSuccess) {
-        delete s;
-        return hip_fail(e, "hipMalloc(reconstruction set)");
-    }
-    e = hipMemset(s->d_set, 0, words * sizeof(uint32_t));
-    if (e == hipSuccess)
-        e = hipMemcpy(s->d_set, dir.data(), dir.size() * sizeof(ReconSetEntry), hipMemcpyHostToDevice);
-    for (unsigned i = 0; i < nplans && e == hipSuccess; ++i) {
-        const ezrs_recon *p = plans[i];
-        e = hipMemcpy(s->d_set + dir[i].off, p->d_tab,
-                      recon_table_words(p->mm, p->nroots, p->nsurv, p->nlost) * sizeof(uint32_t),
-                      hipMemcpyDeviceToDevice);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);   // the plans may be destroyed at once
-    if (e != hipSuccess) {
-        ezrs_recon_set_destroy(s);
-        return hip_fail(e, "copy of the plans' tables (reconstruction set)");
-    }
-    *out = s;
-    return 0;
+    return create_set(out, plans, nplans, "reconstruction set", [](const ezrs_recon &p) {
+        return std::make_pair(p.nsurv, p.nlost);
+    }, true);
 }
 
-int ezrs_recon_set_destroy(ezrs_recon_set *s) {
-    if (!s) return 0;
-    DeviceGuard g(s->device);
-    if (s->d_set) (void)hipFree(s->d_set);
-    delete s;
-    return 0;
-}
+int ezrs_recon_set_destroy(ezrs_recon_set *s) { return destroy_set(s); }
 
 int ezrs_reconstruct_ptrs_mixed(const ezrs_recon_set *s, const uint32_t *plan_of, void *const *table,
                                 size_t table_pitch, size_t shard_len, size_t nstripes, unsigned align,
@@ -1125,10 +1145,42 @@ int ezrs_reconstruct_ptrs_mixed(const ezrs_recon_set *s, const uint32_t *plan_of
         return r < 0 ? r : 0;
     // nsurv, nlost: per stripe, from the directory
     ReconMixedArgs a{{{{nullptr, 0, 0, shard_len, 0, 0, 0, 0}, result, 0, 0, s->mm, recon_row_pad(s->nroots),
-                       result ? s->nroots : s->max_nlost}, table, table_pitch, 0}, plan_of, s->d_set, s->nplans};
+                       result ? s->nroots : s->most}, table, table_pitch, 0}, plan_of, s->d_set, s->nplans};
     DeviceGuard g(s->device);
     hipError_t e = launch_recon(a, nstripes, align, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return hip_fail(e, "reconstruction launch");
+    return 0;
+}
+
+// An update plan's table is the image of a reconstruction with survivors = changed and lost = the
+// parity positions.
+int ezrs_update_set_create(ezrs_update_set **out, const ezrs_update *const *plans, unsigned nplans) {
+    return create_set(out, plans, nplans, "update set", [](const ezrs_update &p) {
+        return std::make_pair(p.nchg, p.nroots);
+    }, false);
+}
+
+int ezrs_update_set_destroy(ezrs_update_set *s) { return destroy_set(s); }
+
+int ezrs_update_ptrs_mixed(const ezrs_update_set *s, const uint32_t *plan_of, void *const *table,
+                           size_t table_pitch, const void *const *new_table, size_t new_pitch,
+                           size_t shard_len, size_t nstripes, unsigned align, void *stream) {
+    if (!s || !plan_of || !table || !new_table) return -EINVAL;
+    const size_t w = s->mm <= 8 ? 1 : 2;
+    if (new_pitch < s->most) {
+        g_last_error = "update_ptrs_mixed: new_pitch below the largest nchanged of the set";
+        return -EINVAL;
+    }
+    if (int r = batch_check("update_ptrs_mixed", table_pitch, (size_t)s->len + s->nroots, shard_len,
+                            nstripes, align, w))
+        return r < 0 ? r : 0;
+    // nchg: per stripe, from the directory; here the set's largest
+    UpdateMixedArgs a{{{{nullptr, 0, 0, shard_len, 0, 0, 0, 0}, nullptr, 0, 0, s->most, s->len, s->nroots, s->mm,
+                        recon_row_pad(s->nroots)}, table, new_table, table_pitch, new_pitch, 0},
+                      plan_of, s->d_set, s->nplans};
+    DeviceGuard g(s->device);
+    hipError_t e = launch_update(a, nstripes, align, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "update launch");
     return 0;
 }
 

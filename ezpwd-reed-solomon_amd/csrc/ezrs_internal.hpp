@@ -348,6 +348,17 @@ struct ReconMixedArgs : ReconBatchArgs {
     const uint32_t *set;          // the directory is at its head
     unsigned nplans;
 };
+// The mixed batched update (ezrs_update_ptrs_mixed): UpdateBatchArgs with a change set per stripe,
+// from a set of update plans (ezrs_update_set_create) laid out as above.  An update plan's table is
+// a recon_table image with survivors = changed and lost = the parity positions, so its directory
+// entry reads (off, nchanged, nroots, offset of the changed list).  nchg here is the largest
+// nchanged of the set, which the kernel does not use (a stripe takes its own plan's); len, nroots,
+// mm and nrp hold for every plan of the set.
+struct UpdateMixedArgs : UpdateBatchArgs {
+    const uint32_t *plan_of;      // [nstripes], device
+    const uint32_t *set;          // the directory is at its head
+    unsigned nplans;
+};
 // t: the plan's device table (table_view of its base).  The pointer forms: al is the OR of the
 // addresses in a.tab that the call uses; the batched forms: the alignment the caller promises for
 // every pointer of the tables.
@@ -358,5 +369,6 @@ hipError_t launch_update(const UpdatePtrArgs &a, size_t al, const DevTable &t, h
 hipError_t launch_recon(const ReconBatchArgs &a, size_t nstripes, size_t al, const DevTable &t, hipStream_t s);
 hipError_t launch_update(const UpdateBatchArgs &a, size_t nstripes, size_t al, const DevTable &t, hipStream_t s);
 hipError_t launch_recon(const ReconMixedArgs &a, size_t nstripes, size_t al, hipStream_t s);
+hipError_t launch_update(const UpdateMixedArgs &a, size_t nstripes, size_t al, hipStream_t s);
 
 } // namespace ezrs

@@ -42,7 +42,8 @@
 // one pointer per row and stripe in a table in device memory (ezrs_reconstruct_ptrs_batch /
 // ezrs_update_ptrs_batch: many such stripes per call).  In the batch forms a wave never spans two
 // stripes, so all a plan contributes is uniform over the wave; ezrs_reconstruct_ptrs_mixed
-// (ReconMixedArgs) therefore chooses the plan per stripe, from a set of plans in one allocation.
+// (ReconMixedArgs) and ezrs_update_ptrs_mixed (UpdateMixedArgs) therefore choose the plan per
+// stripe, from a set of plans in one allocation.
 #include <algorithm>
 #include <cerrno>
 #include <new>
@@ -286,7 +287,7 @@ template <class A>
 constexpr bool kTable = std::is_same_v<A, ReconPtrArgs> || std::is_same_v<A, UpdatePtrArgs>;
 template <class A>
 constexpr bool kBatch = std::is_same_v<A, ReconBatchArgs> || std::is_same_v<A, UpdateBatchArgs> ||
-                        std::is_same_v<A, ReconMixedArgs>;
+                        std::is_same_v<A, ReconMixedArgs> || std::is_same_v<A, UpdateMixedArgs>;
 
 // The lane map of the batch forms.  A stripe takes a.wruns threads, its runs rounded up to a wave,
 // so a wave never spans two stripes: wave w of the launch works on stripe s = w / (wruns / 64) of
@@ -331,7 +332,8 @@ struct At {
             live = batch_lane(a, epl, f, j);
             base = nullptr;
             trow = (Slot *)a.table + f * a.pitch;
-            if constexpr (std::is_same_v<A, UpdateBatchArgs>) nrow = (Slot *)a.new_table + f * a.new_pitch;
+            if constexpr (std::is_same_v<A, UpdateBatchArgs> || std::is_same_v<A, UpdateMixedArgs>)
+                nrow = (Slot *)a.new_table + f * a.new_pitch;
         } else if constexpr (TABLE) {
             f = 0;
             j = a.span.j0 + t * epl;
@@ -630,10 +632,11 @@ __global__ void __launch_bounds__(256) k_recon(A a, const uint32_t *__restrict__
 // where it is stored.  Either way its bits above the symbol stay as they were (the columns are
 // symbols, and so is `fix`).
 
-// N changed positions from c0: the old and the new symbols, loaded together; d = old ^ new.
-template <typename T, int V, int N, class A>
+// N changed positions from c0: the old and the new symbols, loaded together; d = old ^ new.  KP,
+// here and below: the pointer type of the plan's table, as in sweep.
+template <typename T, int V, int N, class A, class KP>
 __device__ __forceinline__ void udelta(const At<T, A> &at, const T *nbase,
-                                       const uint32_t *__restrict__ chg, unsigned c0,
+                                       KP __restrict__ chg, unsigned c0,
                                        uint32_t (&d)[N][Run<T, V>::ND], uint32_t (&nw)[N][Run<T, V>::ND]) {
     using R = Run<T, V>;
 #pragma unroll
@@ -649,8 +652,8 @@ __device__ __forceinline__ void udelta(const At<T, A> &at, const T *nbase,
 
 // The N deltas of the positions from c0 into the accumulators of a row block; K: the coefficients,
 // already at the block's first row.  m = 8 takes them in pairs.
-template <typename T, int RB, int V, int MB, int N>
-__device__ __forceinline__ void ufeed(const UpdateArgs &a, const uint32_t *__restrict__ K, unsigned c0,
+template <typename T, int RB, int V, int MB, int N, class KP>
+__device__ __forceinline__ void ufeed(const UpdateArgs &a, KP __restrict__ K, unsigned c0,
                                       const uint32_t (&d)[N][Run<T, V>::ND],
                                       uint32_t (&acc)[RB][Run<T, V>::ND]) {
     constexpr int ND = Run<T, V>::ND;
@@ -672,6 +675,15 @@ __device__ __forceinline__ void ufeed(const UpdateArgs &a, const uint32_t *__res
     }
 }
 
+// The changed positions of the lane's stripe: the plan's, or in the mixed form the stripe's own plan's
+// (nchg, from the directory).  The one-plan forms read a.nchg where they use it, as they did before
+// there was a mixed form: with a copy handed down instead, seven of them compiled to other streams.
+template <class A>
+__device__ __forceinline__ unsigned changed_count(const A &a, unsigned nchg) {
+    if constexpr (std::is_same_v<A, UpdateMixedArgs>) return nchg;
+    else return a.nchg;
+}
+
 // By the accumulator registers of a row block (RB x dwords of the run), what keeps every
 // instantiation clear of spills and all but the two largest at four or more waves per SIMD
 // (resource report in DESIGN section 4): whether the old parity is loaded ahead of the arithmetic
@@ -681,11 +693,11 @@ constexpr bool uearly(int accs) { return accs < 64; }
 constexpr int ugroup(int accs) { return accs >= 128 ? 2 : (int)kUnroll; }
 constexpr unsigned ukeep(int accs) { return accs >= 128 ? 1 : accs >= 64 ? 2 : kUnroll; }
 
-// One row block.  NC != 0: the plan's NC deltas are in d.  NC == 0: all changed positions are read
-// (again), a group's loads issued together, the ragged end one by one.
-template <typename T, int RB, int V, int MB, int NC, class A>
+// One row block.  NC != 0: the plan's NC deltas are in d.  NC == 0: all nchg changed positions are
+// read (again), a group's loads issued together, the ragged end one by one.
+template <typename T, int RB, int V, int MB, int NC, class A, class KP>
 __device__ __forceinline__ void usweep(const At<T, A> &at, const T *nbase,
-                                       const uint32_t *__restrict__ chg, const uint32_t *__restrict__ K,
+                                       KP __restrict__ chg, unsigned nchg, KP __restrict__ K,
                                        const uint32_t (&d)[NC ? NC : 1][Run<T, V>::ND],
                                        uint32_t (&acc)[RB][Run<T, V>::ND]) {
     constexpr int ND = Run<T, V>::ND, G = ugroup(RB * ND);
@@ -694,12 +706,12 @@ __device__ __forceinline__ void usweep(const At<T, A> &at, const T *nbase,
         ufeed<T, RB, V, MB, NC>(a, K, 0, d, acc);
     } else {
         unsigned c = 0;
-        for (; c + G <= a.nchg; c += G) {
+        for (; c + G <= changed_count(a, nchg); c += G) {
             uint32_t e[G][ND], w[G][ND];
             udelta<T, V, G>(at, nbase, chg, c, e, w);
             ufeed<T, RB, V, MB, G>(a, K, c, e, acc);
         }
-        for (; c < a.nchg; ++c) {
+        for (; c < changed_count(a, nchg); ++c) {
             uint32_t e[1][ND], w[1][ND];
             udelta<T, V, 1>(at, nbase, chg, c, e, w);
             ufeed<T, RB, V, MB, 1>(a, K, c, e, acc);
@@ -713,10 +725,9 @@ __device__ __forceinline__ void usweep(const At<T, A> &at, const T *nbase,
 // (Deltas kept across several blocks are not built: the compiler then hoists every bit mask and
 // selector of every delta out of the block loop and the kernels need 160 - 256 VGPRs.)  Either way
 // the data is overwritten only after the last block.
-template <typename T, int RB, int V, int NC, class A>
-__device__ __forceinline__ void ubody(const At<T, A> &at, const uint32_t *__restrict__ K,
-                                      const uint32_t *__restrict__ chg, const uint32_t *__restrict__ fix,
-                                      const T *nbase) {
+template <typename T, int RB, int V, int NC, class A, class KP>
+__device__ __forceinline__ void ubody(const At<T, A> &at, KP __restrict__ K, KP __restrict__ chg,
+                                      unsigned nchg, KP __restrict__ fix, const T *nbase) {
     using R = Run<T, V>;
     constexpr int ND = R::ND;
     const A &a = at.a;
@@ -741,9 +752,9 @@ __device__ __forceinline__ void ubody(const At<T, A> &at, const uint32_t *__rest
 #pragma unroll
                 for (int i = 0; i < ND; ++i) acc[r][i] = 0;
         }
-        const uint32_t *const Kb = K + (sizeof(T) == 1 ? 2 * r0 : r0);
-        if (a.mm == 8) usweep<T, RB, V, 8, NC>(at, nbase, chg, Kb, d, acc);
-        else usweep<T, RB, V, 0, NC>(at, nbase, chg, Kb, d, acc);
+        const KP Kb = K + (sizeof(T) == 1 ? 2 * r0 : r0);
+        if (a.mm == 8) usweep<T, RB, V, 8, NC>(at, nbase, chg, nchg, Kb, d, acc);
+        else usweep<T, RB, V, 0, NC>(at, nbase, chg, nchg, Kb, d, acc);
 #pragma unroll
         for (int r = 0; r < RB; ++r)
             if (r0 + r < a.nroots) {
@@ -767,7 +778,7 @@ __device__ __forceinline__ void ubody(const At<T, A> &at, const uint32_t *__rest
         for (int u = 0; u < NC; ++u) R::store(at.row(chg[u], u), nw[u]);
     } else {
         for (unsigned r0 = 0; r0 < a.nroots; r0 += RB) block(r0);
-        for (unsigned c = 0; c < a.nchg; ++c) {
+        for (unsigned c = 0; c < changed_count(a, nchg); ++c) {
             uint32_t x[ND];
             R::load(at.fresh(nbase, c), x);
             R::store(at.row(chg[c], c), x);
@@ -775,7 +786,15 @@ __device__ __forceinline__ void ubody(const At<T, A> &at, const uint32_t *__rest
     }
 }
 
-// K: the coefficients of the changed positions; chg: the positions; fix: [nrp] (recon_table).
+// K: the coefficients of the changed positions; chg: the positions; fix: [nrp] (recon_table).  The
+// mixed form (UpdateMixedArgs) gets three null pointers and takes all of that, and the number of
+// changed positions, per stripe, as k_recon's mixed form does: the plan index, the plan's directory
+// entry and the parts of the plan's image are dependent scalar loads through the constant address
+// space at the top of the wave (nothing the call writes may overlap plan_of or the set; the NC = 0
+// body reads the image and the pointer tables again after its first parity stores).  A stripe whose
+// index names no plan returns before anything is asked of either pointer table.  RB serves the whole
+// set, NROOTS being the same for all its plans; whether the deltas stay in registers is decided per
+// stripe, a wave-uniform branch to one of the bodies below.
 template <typename T, int RB, int V, class A>
 __global__ void __launch_bounds__(256) k_update(A a, const uint32_t *__restrict__ K,
                                                 const uint32_t *__restrict__ chg,
@@ -787,20 +806,41 @@ __global__ void __launch_bounds__(256) k_update(A a, const uint32_t *__restrict_
     const At<T, A> at(a, t, R::EPL);
     if constexpr (kBatch<A>)                        // nothing has been asked for yet
         if (!at.live) return;
+    constexpr bool MIXED = std::is_same_v<A, UpdateMixedArgs>;
+    // the mixed form's count (changed_count), set below.  Its initial value is never used; started
+    // from 0 instead, five mixed forms took more registers (u8 RB = 4 at V = 1: 53 against 32; both
+    // sets of figures are in profiles/recon/isa_stats_update_mixed.txt).  Only registers hang on it.
+    unsigned nchg = MIXED ? a.nchg : 0;
+    typedef __attribute__((address_space(4))) const uint32_t Word;
+    std::conditional_t<MIXED, Word *, const uint32_t *> Kt, ct, ft;   // the plan's table, by part
+    if constexpr (MIXED) {
+        const uint32_t pi = __builtin_amdgcn_readfirstlane(((Word *)a.plan_of)[at.f]);
+        if (pi >= a.nplans) return;
+        // (off, nchg, nroots, pos): an update plan's image has survivors = changed, lost = the parity
+        Word *const set = (Word *)a.set, *const ent = set + (size_t)pi * (sizeof(ReconSetEntry) / 4);
+        nchg = ent[1];
+        Kt = set + ent[0];
+        ct = set + ent[3];
+        ft = ct + nchg + a.nroots;
+    } else {
+        Kt = K;
+        ct = chg;
+        ft = fix;
+    }
     const T *const nbase = at.fresh0();
     static_assert(kUnroll == 4, "one case per count of changed positions kept in registers");
     constexpr unsigned KEEP = ukeep(RB * R::ND);
-    const unsigned nc = a.nroots <= RB && a.nchg <= KEEP ? a.nchg : 0;
+    const unsigned nc = a.nroots <= RB && changed_count(a, nchg) <= KEEP ? changed_count(a, nchg) : 0;
     if (nc == 1) {
-        ubody<T, RB, V, 1>(at, K, chg, fix, nbase);
+        ubody<T, RB, V, 1>(at, Kt, ct, nchg, ft, nbase);
     } else if (nc == 2) {
-        if constexpr (KEEP >= 2) ubody<T, RB, V, 2>(at, K, chg, fix, nbase);
+        if constexpr (KEEP >= 2) ubody<T, RB, V, 2>(at, Kt, ct, nchg, ft, nbase);
     } else if (nc == 3) {
-        if constexpr (KEEP >= 4) ubody<T, RB, V, 3>(at, K, chg, fix, nbase);
+        if constexpr (KEEP >= 4) ubody<T, RB, V, 3>(at, Kt, ct, nchg, ft, nbase);
     } else if (nc == 4) {
-        if constexpr (KEEP >= 4) ubody<T, RB, V, 4>(at, K, chg, fix, nbase);
+        if constexpr (KEEP >= 4) ubody<T, RB, V, 4>(at, Kt, ct, nchg, ft, nbase);
     } else {
-        ubody<T, RB, V, 0>(at, K, chg, fix, nbase);
+        ubody<T, RB, V, 0>(at, Kt, ct, nchg, ft, nbase);
     }
 }
 
@@ -939,6 +979,9 @@ hipError_t launch_update(const UpdateBatchArgs &a, size_t nstripes, size_t al, c
 }
 hipError_t launch_recon(const ReconMixedArgs &a, size_t nstripes, size_t al, hipStream_t s) {
     return recon_any(a, nstripes, al, DevTable{}, s);   // !a.nrows: no result and no plan that rebuilds
+}
+hipError_t launch_update(const UpdateMixedArgs &a, size_t nstripes, size_t al, hipStream_t s) {
+    return update_any(a, nstripes, al, DevTable{}, s);  // a.nchg: the set's largest, never 0
 }
 
 } // namespace ezrs

@@ -115,6 +115,9 @@ def lib():
         L.ezrs_recon_set_create.argtypes = [C.POINTER(_vp), _vp, _u]
         L.ezrs_recon_set_destroy.argtypes = [_vp]
         L.ezrs_reconstruct_ptrs_mixed.argtypes = [_vp, _vp, _vp, _sz, _sz, _sz, _u, _vp, _vp]
+        L.ezrs_update_set_create.argtypes = [C.POINTER(_vp), _vp, _u]
+        L.ezrs_update_set_destroy.argtypes = [_vp]
+        L.ezrs_update_ptrs_mixed.argtypes = [_vp, _vp, _vp, _sz, _vp, _sz, _sz, _sz, _u, _vp]
         L.ezrs_decode_ptrs_workspace_bytes.restype = _sz
         L.ezrs_decode_ptrs_workspace_bytes.argtypes = [_vp, _u, _sz, _sz]
         L.ezrs_decode_ptrs.argtypes = [_vp, _vp, _u, _sz, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _sz, _vp]
@@ -908,6 +911,57 @@ class Update(_Plan):
         _check(lib().ezrs_update_ptrs_batch(self._h, _tp(table), pitch, _tp(new_table), new_pitch, shard_len,
                                             nstripes, align, _stream_ptr(stream)),
                "ezrs_update_ptrs_batch")
+
+
+class UpdateSet(_Plan):
+    """A set of parity-update plans of one codec, length and device (ezrs_update_set_create), for
+    ``apply_ptrs_mixed``: the batched pointer form with a change set per stripe.  The set copies
+    the plans' tables; it keeps nothing of the plans or the codec.
+
+    * ``nplans``    the number of plans; an index at or above it (``PLAN_SKIP``) skips a stripe
+    * ``nchanged``  the plans' nchanged, by index; new_table needs a pitch of at least the largest"""
+
+    _destroy = "ezrs_update_set_destroy"
+
+    def __init__(self, plans):
+        plans = list(plans)
+        for i, p in enumerate(plans):
+            if not isinstance(p, Update) or not p._h:
+                raise EzrsError(f"plans[{i}]: expected an Update plan")
+        self.nplans, self.nchanged = len(plans), [p.nchanged for p in plans]
+        arr = (_vp * max(len(plans), 1))(*[p._h for p in plans])
+        h = _vp()
+        self._h = None
+        _check(lib().ezrs_update_set_create(C.byref(h), arr, len(plans)), "ezrs_update_set_create")
+        self._h = h
+        self.length, self.nroots, self.device, self._w = (plans[0].length, plans[0].nroots, plans[0].device,
+                                                          plans[0]._w)
+
+    def apply_ptrs_mixed(self, table, new_table, plan_of, shard_len, align=None, stream=None):
+        """ezrs_update_ptrs_mixed: table, new_table, shard_len, align and stream as in
+        ``Update.apply_ptrs_batch``; plan_of: an int32 or uint32 device tensor of at least nstripes
+        entries, stripe s working under plan plan_of[s] of the set.  Of table[s] only the entries at
+        that plan's changed positions and at the parity positions are used, of new_table[s] only
+        the first nchanged of that plan, in the order of its ``changed``; new_table's pitch is at
+        least the largest nchanged of the set.  A stripe whose index is not below ``nplans`` is
+        skipped: nothing of it is read or written.  Two stripes of one call must not be the same
+        physical stripe.  Both tables and plan_of are read while the kernels run."""
+        import torch
+        nstripes, pitch = self._ptr_table(table, "table", self.length + self.nroots)
+        nnew, new_pitch = self._ptr_table(new_table, "new_table", max(self.nchanged))
+        if nnew != nstripes:
+            raise EzrsError(f"new_table: {nnew} stripes, table has {nstripes}")
+        shard_len, align = int(shard_len), self._align(align)
+        if shard_len < 0:
+            raise EzrsError("shard_len: negative")
+        _dev_rows(plan_of, "plan_of", self.device, 4, ndim=1)
+        if plan_of.dtype not in (torch.int32, torch.uint32):
+            raise EzrsError(f"plan_of: expected int32 or uint32 entries, got {plan_of.dtype}")
+        if plan_of.shape[0] < nstripes:
+            raise EzrsError("plan_of: fewer entries than stripes")
+        _check(lib().ezrs_update_ptrs_mixed(self._h, _tp(plan_of), _tp(table), pitch, _tp(new_table), new_pitch,
+                                            shard_len, nstripes, align, _stream_ptr(stream)),
+               "ezrs_update_ptrs_mixed")
 
 
 def ptr_table(stripes, optional=()):

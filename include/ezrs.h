@@ -445,9 +445,8 @@ int ezrs_update_ptrs_batch(const ezrs_update *plan, void *const *table, size_t t
  * Checked on the host before any launch.  -EINVAL: null set, plan_of or `table`; table_pitch < len +
  * NROOTS; align not 16, 4 or the datum size; shard_len * datum bytes or nstripes * shard_len
  * overflowing size_t.  Otherwise nstripes == 0 or shard_len == 0 returns 0 and touches nothing.
- * The strided form and the update forms have no mixed variant: in the strided lane map a wave may
- * span two frames, so a plan per frame would not be uniform over a wave, and update plans differ per
- * stripe in the changed positions and in the rows of new_table. */
+ * The strided forms have no mixed variant: in the strided lane map a wave may span two frames, so
+ * a plan per frame would not be uniform over a wave.  The batched update has one, below. */
 typedef struct ezrs_recon_set ezrs_recon_set;
 #define EZRS_PLAN_SKIP 0xFFFFFFFFu   /* in plan_of: leave this stripe alone */
 int ezrs_recon_set_create(ezrs_recon_set **out, const ezrs_recon *const *plans, unsigned nplans);
@@ -455,6 +454,49 @@ int ezrs_recon_set_destroy(ezrs_recon_set *set);   /* NULL: 0 */
 int ezrs_reconstruct_ptrs_mixed(const ezrs_recon_set *set, const uint32_t *plan_of,
                                 void *const *table, size_t table_pitch, size_t shard_len,
                                 size_t nstripes, unsigned align, int32_t *result, void *stream);
+
+/* Mixed-plan batched parity update (device-resident): ezrs_update_ptrs_batch with a change set per
+ * stripe, for a flush of small writes in which one stripe's write hit data shard 3, the next one's
+ * shard 7 and a third touched two shards.  One call on the resident table, with no bucketing by
+ * change set on the host, no compacted table pair per bucket and no launch per bucket.
+ *   ezrs_update_set_create   gathers nplans existing update plans into one device allocation, in
+ *            every rule as ezrs_recon_set_create does for reconstruction plans: a directory (per
+ *            plan: where its table lies, nchanged) and copies of the plans' device tables; valid
+ *            after the plans and the codec are destroyed, const afterwards, shareable; the same
+ *            change set may appear more than once.  -EINVAL, before any device is touched: null
+ *            `out` or `plans`; nplans == 0; a NULL entry; plans that differ in symbol bits, NROOTS,
+ *            len or device.  -ENOTSUP: the allocation would exceed 64 MiB.  -ENOMEM; -EIO for a HIP
+ *            failure.  Plans of different codecs with equal symbol bits, NROOTS and len are NOT
+ *            detected: each stripe simply gets its plan's columns.
+ *   ezrs_update_ptrs_mixed   stripe s works under plan plan_of[s] of the set.  plan_of: a DEVICE
+ *            array of nstripes indices on the set's device, read WHILE THE KERNELS RUN, like the
+ *            tables.  Per stripe the call is exactly ezrs_update_ptrs_batch under that stripe's
+ *            plan: the same bytes are written to the parity shards and to the changed shards; the
+ *            old parity is read, not recomputed; the data is overwritten after the parity; bits
+ *            above the symbol as there.  Of table[s*table_pitch + .] only the entries at the changed
+ *            positions of THAT STRIPE'S plan and at len..len+NROOTS-1 are used, and of
+ *            new_table[s*new_pitch + r] only r < that plan's nchanged, in the order of that plan's
+ *            `changed`; every other entry of either row may be NULL or garbage.  new_pitch >= the
+ *            largest nchanged of the set.  An index >= nplans skips the stripe (EZRS_PLAN_SKIP): no
+ *            entry of either of its table rows is read and no byte is written.
+ *            Asynchronous; no workspace; never allocates, never synchronises; capturable.
+ * NOT CHECKED, and undefined behaviour when broken: what ezrs_update_ptrs_batch lists, for every
+ * stripe that is not skipped under that stripe's plan; any overlap between a buffer the call writes
+ * and plan_of or the set; and two stripes of one call that name the same physical stripe (two
+ * writes to one stripe in one flush): they race on its parity.  Merge those into one plan with the
+ * union of the changed positions, or issue two calls.
+ * Checked on the host before any launch.  -EINVAL: null set, plan_of, `table` or `new_table`;
+ * table_pitch < len + NROOTS; new_pitch < the largest nchanged of the set; align not 16, 4 or the
+ * datum size; shard_len * datum bytes or nstripes * shard_len overflowing size_t.  Otherwise
+ * nstripes == 0 or shard_len == 0 returns 0 and touches nothing.
+ * A change set that differs from codeword to codeword within a stripe is not built. */
+typedef struct ezrs_update_set ezrs_update_set;
+int ezrs_update_set_create(ezrs_update_set **out, const ezrs_update *const *plans, unsigned nplans);
+int ezrs_update_set_destroy(ezrs_update_set *set);   /* NULL: 0 */
+int ezrs_update_ptrs_mixed(const ezrs_update_set *set, const uint32_t *plan_of,
+                           void *const *table, size_t table_pitch,
+                           const void *const *new_table, size_t new_pitch,
+                           size_t shard_len, size_t nstripes, unsigned align, void *stream);
 
 /* Pointer forms of ezrs_decode_interleaved (device-resident): the error path of the pointer forms
  * above.  A stripe whose verify or rebuild reported -1 holds errors at unknown positions; these

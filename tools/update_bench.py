@@ -7,6 +7,7 @@ comparison shares a kernel with the update.
     python tools/update_bench.py [--gib 1.0] [--out profiles/update/update_bench.json]
     python tools/update_bench.py --ptrs [--gib 1.0] [--out profiles/update/update_ptrs_bench.json]
     python tools/update_bench.py --batch [--gib 1.0] [--out profiles/update/update_batch_bench.json]
+    python tools/update_bench.py --mixed [--gib 1.0] [--out profiles/update/update_mixed_bench.json]
 
 One frame per shape: len + nroots shards of `depth` symbols, symbol stride = depth, sized so that
 the frame holds at least --gib GiB (well past the 256 MiB Infinity Cache); newsyms is a packed
@@ -40,7 +41,25 @@ a random permutation.
   batch_inframe  the batch call on tables of pointers to the rows of the strided frames and of
            their newsyms: the same addresses as the strided call, so that the kernels' addressing
            is compared apart from where the shards lie
-batch_over_loop, batch_over_strided and inframe_over_strided are the ratios of the medians."""
+batch_over_loop, batch_over_strided and inframe_over_strided are the ratios of the medians.
+
+--mixed: a flush of small writes in which every stripe has a change set of its own, RS(255,251) at
+len 10 with shards of 4 KiB and 64 KiB, so many stripes that the shards the update touches (changed,
+parity, new symbols; nothing else is on the device) hold at least --gib GiB, each a buffer of its
+own in one pool, placed by a random permutation.  Two mixes, ten plans each, stripe s under plan
+s % 10: "one changed" (stripe s changes position s % 10) and "1..5 changed" (stripe s changes
+1 + s % 5 positions, (s + 3 i) % 10: five kernel bodies in one launch).  Five calls alternate in
+the same process as above:
+  buckets    ten ezrs_update_ptrs_batch calls, one per plan, each on its own compacted table and
+             new_table; the bucketing and the compacted tables are made once, outside the timed region
+  mixed      one ezrs_update_ptrs_mixed call on the resident tables, ten plans
+  batch_one  one ezrs_update_ptrs_batch call with every stripe under plan 0 (one changed position),
+             on a table that names each stripe's first changed shard at that plan's position: the
+             same buffers, and what a call costs that fetches no plan
+  mixed_one  the mixed call with a set of that one plan and plan_of all zero, on the same table
+  batch_one_again   batch_one a second time: what two timings of the same call differ by
+mixed_over_buckets, mixed_one_over_batch_one and batch_again_over_batch_one are the ratios of the
+medians.  Not measured: the host's bucketing, plans with large tables."""
 import ctypes as C
 import argparse
 import json
@@ -241,17 +260,135 @@ def main_batch(args):
     return out
 
 
+MIXED_SHARD_BYTES = [4 << 10, 64 << 10]
+MIXES = [
+    # (name, the changed positions of stripe s)
+    ("one changed: [s % 10]", lambda s: [s % 10]),
+    ("1..5 changed: 1 + s % 5 positions (s + 3 i) % 10", lambda s: [(s + 3 * i) % 10 for i in range(1 + s % 5)]),
+]
+
+
+def main_mixed(args):
+    L, sp = ezrs.lib(), ezrs._stream_ptr(None)
+    out = {"gib": args.gib, "reps": REPS, "device": torch.cuda.get_device_name(0), "results": []}
+    length, NP = 10, 10
+    for mix, changed_of in MIXES:
+        for n in MIXED_SHARD_BYTES:                 # 1-byte symbols
+            c = ezrs.Codec.rs(255, 251)
+            NR = c.nroots
+            S = length + NR
+            lists = [changed_of(k) for k in range(NP)]
+            assert all(changed_of(k) == lists[k % NP] for k in range(4 * NP))
+            per10 = sum(2 * len(ch) + NR for ch in lists)               # buffers of ten stripes
+            ns = max(NP, -(-int(args.gib * (1 << 30)) * NP // (per10 * n)))
+            maxchg = max(len(ch) for ch in lists)
+            # slots of stripe s: changed [k] | parity [NR] | new symbols [k]
+            first, T = [], 0
+            for s in range(ns):
+                first.append(T)
+                T += 2 * len(lists[s % NP]) + NR
+            perm = torch.randperm(T, generator=torch.Generator().manual_seed(2)).tolist()
+            g = torch.Generator(device="cuda").manual_seed(1)
+            pool = torch.empty((T, n), dtype=torch.uint8, device="cuda")
+            step = max(1, (256 << 20) // n)
+            for t0 in range(0, T, step):
+                blk = pool[t0:t0 + step]
+                blk.copy_(torch.randint(0, 256, blk.shape, generator=g, device="cuda", dtype=torch.uint8))
+            assert pool.data_ptr() % 16 == 0
+            base = pool.data_ptr()
+            tab = [[0] * S for _ in range(ns)]      # an entry no plan of the stripe uses: NULL
+            tab1 = [[0] * S for _ in range(ns)]
+            ntab = [[0] * maxchg for _ in range(ns)]
+            written = []
+            for s in range(ns):
+                ch = lists[s % NP]
+                k, f = len(ch), first[s]
+                for r, p in enumerate(ch):
+                    tab[s][p] = base + perm[f + r] * n
+                    ntab[s][r] = base + perm[f + k + NR + r] * n
+                tab1[s][lists[0][0]] = base + perm[f] * n
+                for i in range(NR):
+                    tab[s][length + i] = tab1[s][length + i] = base + perm[f + k + i] * n
+                written += perm[f:f + k + NR]
+            table = torch.tensor(tab, dtype=torch.int64).cuda()
+            table_one = torch.tensor(tab1, dtype=torch.int64).cuda()
+            ntable = torch.tensor(ntab, dtype=torch.int64).cuda()
+            written = torch.tensor(written, dtype=torch.int64).cuda()
+            del tab, tab1, ntab
+            orig = pool.clone()
+            plans = [c.update_plan(length, ch) for ch in lists]
+            assert len(lists[0]) == 1
+            uset, uset1 = ezrs.UpdateSet(plans), ezrs.UpdateSet(plans[:1])
+            plan_of = (torch.arange(ns, dtype=torch.int32) % NP).cuda()
+            zeros = torch.zeros(ns, dtype=torch.int32, device="cuda")
+            # the parent's way, prepared: per plan the compacted table and new_table
+            sub = [(table[k::NP].contiguous(), ntable[k::NP].contiguous()) for k in range(NP)]
+            calls = [(plans[k]._h, sub[k][0].data_ptr(), sub[k][1].data_ptr(), sub[k][0].shape[0]) for k in range(NP)]
+
+            def buckets():
+                for h, t, nt, nb in calls:
+                    L.ezrs_update_ptrs_batch(h, t, S, nt, maxchg, n, nb, 16, sp)
+
+            def batch_one():
+                return L.ezrs_update_ptrs_batch(plans[0]._h, table_one.data_ptr(), S, ntable.data_ptr(), maxchg, n,
+                                                ns, 16, sp)
+
+            fns = {"buckets": buckets,
+                   "mixed": lambda: L.ezrs_update_ptrs_mixed(uset._h, plan_of.data_ptr(), table.data_ptr(), S,
+                                                             ntable.data_ptr(), maxchg, n, ns, 16, sp),
+                   "batch_one": batch_one,
+                   "mixed_one": lambda: L.ezrs_update_ptrs_mixed(uset1._h, zeros.data_ptr(), table_one.data_ptr(), S,
+                                                                 ntable.data_ptr(), maxchg, n, ns, 16, sp),
+                   "batch_one_again": lambda: batch_one()}
+            want = {}
+            for what, fn in fns.items():            # each path once, a nonzero delta, on the same input
+                pool.copy_(orig)
+                r = fn()
+                assert r is None or r == 0, (mix, n, what)
+                torch.cuda.synchronize()
+                got = pool[written]
+                kind = "one" if "one" in what else "mix"
+                want.setdefault(kind, got)
+                assert torch.equal(got, want[kind]) and not torch.equal(got, orig[written]), (mix, n, what)
+                del got
+            fg = figure(fns)
+            torch.cuda.synchronize()
+            rec = {"mix": mix, "shape": "RS(255,251) len 10", "len": length, "nroots": NR, "nplans": NP,
+                   "shard_bytes": n, "nstripes": ns, "touched_bytes": T * n,
+                   "bytes_moved_mixed": sum(3 * len(lists[s % NP]) + 2 * NR for s in range(ns)) * n,
+                   "bytes_moved_one": (3 + 2 * NR) * ns * n}
+            for k, v in fg.items():
+                rec[f"t_{k}_ms"], rec[f"spread_{k}"] = v["median_s"] * 1e3, v["spread"]
+            med = {k: v["median_s"] for k, v in fg.items()}
+            rec["mixed_GBps_moved"] = rec["bytes_moved_mixed"] / med["mixed"] / 1e9
+            rec["batch_one_GBps_moved"] = rec["bytes_moved_one"] / med["batch_one"] / 1e9
+            rec["mixed_over_buckets"] = med["mixed"] / med["buckets"]
+            rec["mixed_one_over_batch_one"] = med["mixed_one"] / med["batch_one"]
+            rec["batch_again_over_batch_one"] = med["batch_one_again"] / med["batch_one"]
+            rec["iters"] = {k: v["iters"] for k, v in fg.items()}
+            out["results"].append(rec)
+            print(json.dumps(rec), flush=True)
+            del pool, orig, table, table_one, ntable, written, sub, calls, plans, uset, uset1, c, fns, want
+            torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gib", type=float, default=1.0)
     ap.add_argument("--ptrs", action="store_true", help="the pointer form against the strided form")
     ap.add_argument("--batch", action="store_true", help="many small stripes: loop, batch call, strided call")
+    ap.add_argument("--mixed", action="store_true",
+                    help="a change set per stripe: a call per plan, one mixed call, one single-plan call")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     args.out = args.out or os.path.join(ROOT, "profiles", "update",
+                                        "update_mixed_bench.json" if args.mixed else
                                         "update_batch_bench.json" if args.batch else
                                         "update_ptrs_bench.json" if args.ptrs else "update_bench.json")
     torch.cuda.set_device(0)
+    if args.mixed:
+        return write(args.out, main_mixed(args))
     if args.batch:
         return write(args.out, main_batch(args))
     if args.ptrs:
